@@ -11,11 +11,16 @@ collective; weights broadcast once from rank 0 over RCCL, edited latents gathere
 Headline schedule (round 3, `--plan partition`): a two-stage clip pipeline (pipeline.ClipPipeline) -- while clip i runs
 its latency-bound 100-step edit loop on one CU partition, clip i+1 runs its timestep-batched forward inversion on the
 complementary partition (hardware queues with disjoint CU masks); every clip's own launches, order and values are those of
-the clip edited alone.  Reported beside it: the same clips one at a time in the reference order (`value_reference_order`),
-one at a time with the timestep-batched inversion (`value_single_clip_batched`, the round-1/2 headline), parity against the
-CPU oracle (`parity`), and BASELINE configs 3/4/5 as sub-benchmarks.
+the clip edited alone.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the headline line (`roofline`, `cpu_baseline` and `parity` are
+null there).  `--full` adds the reported-only legs after the timed steps: the same clips one at a time in the reference order
+(`value_reference_order`), one at a time with the timestep-batched inversion (`value_single_clip_batched`, the round-1/2
+headline) and the pipeline's bit-identity check, the phases of one clip, the roofline, parity against the CPU oracle
+(`parity`), the CPU baseline, and BASELINE configs 3/4/5 as sub-benchmarks.  `--dump-outputs DIR` writes what the last timed
+step returned (edited waveform, original-vocoded waveform, edited latent) as float32 DIR/<name>.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
 import argparse
@@ -44,6 +49,29 @@ T_START = time.time()
 
 def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(out, NC):
+    """What a caller of the timed path receives from one step, copied to the host as float32: edit_clip's (edited waveform,
+    original-vocoded waveform, edited latent) for one clip per step; the edited latents of the NC clips otherwise."""
+    host = lambda t: t.detach().float().cpu().contiguous()          # noqa: E731
+    if NC == 1:
+        return dict(edited_waveform=host(out[0]), original_waveform=host(out[1]), edited_latent=host(out[2]))
+    return dict(edited_latent=host(out))
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy for every array (float32, at most DUMP_LIMIT_BYTES in all)."""
+    import numpy as np
+    total = sum(t.numel() * t.element_size() for t in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit"
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+    log(f"outputs of the last timed step -> {path}: {', '.join(f'{k} {tuple(v.shape)}' for k, v in arrays.items())}")
 
 
 def csrc_hash():
@@ -247,6 +275,12 @@ def main():
     ap.add_argument("--no-share-cfg-rows", action="store_true",
                     help="A/B: every classifier-free-guidance row through the whole U-Net graph (rounds 1-4) instead of computing "
                          "the context-free head once per latent (EditEngine.SHARE_CFG_ROWS)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the reported-only legs: one-clip-at-a-time legs and the pipeline's "
+                         "bit-identity check, phases of one clip, roofline, parity vs the CPU oracle, CPU baseline, BASELINE "
+                         "configs 3 / 4 / 5 (each can still be left out with --no-batched / --no-extras / --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as float32 DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -346,12 +380,15 @@ def main():
                 assert gl.abs().max() > 0, f"all-zero edited latents from rank {r}"
         return dt, gathered
 
-    def timed(schedule, K, W):
-        """K clips (or K groups of NC clips), one after the other on the whole GPU."""
+    last_step = {}
+
+    def timed(schedule, K, W, keep=None):
+        """K clips (or K groups of NC clips), one after the other on the whole GPU.  `keep`: a dict that receives the
+        host copy of the last step's outputs (step_outputs)."""
         def step(seed, waves_):
             torch.manual_seed(seed)
             if NC == 1:
-                return run_clip(waves_[0], schedule)[2]
+                return run_clip(waves_[0], schedule)
             return run_clips(waves_, schedule)
         for i in range(W):
             step(1000 + i, [clip_wave(rank * 100000 + i * NC + j) for j in range(NC)])
@@ -366,16 +403,20 @@ def main():
             # all K draws happen inside the timed region
             if NC == 1 and hasattr(m, "prefetch_noise"):
                 m.next_noise_seed = 2000 + i + 1 if i + 1 < K else None
-            lat.append(step(2000 + i, waves[i]))
-        return finish(t0, lat)
+            out = step(2000 + i, waves[i])
+            lat.append(out[2] if NC == 1 else out)
+        res = finish(t0, lat)
+        if keep is not None:
+            keep.update(step_outputs(out, NC))
+        return res
 
     PLAN = args.plan if NC == 1 else "serial"
     pipe = None
     extra = {}
 
-    def timed_pipeline(K, W):
+    def timed_pipeline(K, W, keep=None):
         """K clips through pipeline.ClipPipeline.  Same waveforms and per-clip seeds as `timed`, so the serial legs below
-        edit the same clips."""
+        edit the same clips.  `keep` as in `timed`."""
         edit_args = (src, tgt, neg, [3.0], [12.0], args.T, args.tstart)
         pipe.warm_up(clip_wave(rank * 100000 + 99), *edit_args, prepare=wave_to_mel, seeds=[999])   # builds the workers
         if W:
@@ -386,7 +427,10 @@ def main():
         adist.barrier()
         t0 = time.perf_counter()
         res = pipe.edit_clips(waves, *edit_args, prepare=wave_to_mel, seeds=[2000 + i for i in range(K)])
-        return finish(t0, [r[2] for r in res])
+        done = finish(t0, [r[2] for r in res])
+        if keep is not None:
+            keep.update(step_outputs(res[-1], 1))
+        return done
 
     log(f"model ready ({m.weights_source}); timing {args.steps} clip(s) after {args.warmup} warm-up")
     if PLAN != "serial":
@@ -395,7 +439,7 @@ def main():
             pipe = ClipPipeline(m, plan=PLAN, edit_cus=args.edit_cus, edit_lanes=args.edit_lanes, launch=args.lane_launch,
                                 timestep_group=args.group, overlap_prep=not args.no_overlap_prep, codec_queue=args.codec_queue,
                                 mask_prep=not args.unmasked_prep)
-            dt, gathered = timed_pipeline(args.steps, args.warmup)
+            dt, gathered = timed_pipeline(args.steps, args.warmup, keep=last_step if args.dump_outputs else None)
         except Exception as e:                                  # noqa: BLE001
             # a driver / container without CU-masked streams (hipExtStreamCreateWithCUMask, HSA_CU_MASK set, <= edit_cus CUs)
             # must still produce a headline: fall back to one clip at a time on the whole GPU
@@ -417,18 +461,20 @@ def main():
                         if getattr(pipe, "codec_queue", "") == "lane" else "")))
         log(f"{PLAN} pipeline: {dt / args.steps:.3f} s/clip  {json.dumps(extra['pipeline'])}")
     else:
-        dt, gathered = timed(args.schedule, args.steps, args.warmup)
+        dt, gathered = timed(args.schedule, args.steps, args.warmup, keep=last_step if args.dump_outputs else None)
         headline = (f"one clip at a time; forward inversion schedule: {args.schedule}"
                     + (f" ({args.group} timesteps per U-Net call)" if args.schedule == "batched" else " (reference order)"))
         log(f"{args.schedule}: {dt / args.steps:.3f} s/clip")
     value = world * NC * args.steps / dt
     # per-rank rates (the driver computes scaling efficiency from `value`; these show whether one rank lags)
     per_rank = adist.per_rank_rates(NC * args.steps, dt_local, dev) if grouped else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step)
 
     # ---- the same clips ONE AT A TIME (same waveforms, same seeds): reference order, and the timestep-batched inversion.
     # Every one of the 600 sample-forwards of a clip is computed in all three schedules; batched only regroups the
     # inversion's U-Net calls (the edit-friendly inversion draws all x_t independently from x_0, models.py:67-83).
-    if not args.no_batched:
+    if args.full and not args.no_batched:
         n_ser = max(1, min(args.serial_clips, args.steps)) if PLAN != "serial" else args.steps
         legs = {}
         for sched_name in ("sequential", "batched"):
@@ -476,7 +522,7 @@ def main():
 
     # ---- where one clip's time goes when it has the GPU to itself (single-clip latency mode: batched inversion)
     phases = None
-    if rank == 0 and NC == 1 and not args.no_batched:
+    if args.full and rank == 0 and NC == 1 and not args.no_batched:
         try:                    # reported-only leg: the headline line must survive a failure here
             pa = argparse.Namespace(**vars(args))
             pa.schedule = "batched"
@@ -492,7 +538,7 @@ def main():
     # op's share of a forward.  `achieved` prices EXECUTED flops (2MNK of every launch; the folded cross-attention executes
     # fewer than the reference formulation it replaces) -- the algorithmic count is used for the path-level figures only.
     roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         roof = roofline_leg(m, pipe, args, NC, dt)
         if roof is not None:
             try:
@@ -502,7 +548,7 @@ def main():
                 roof = dict(failed=str(e), bound=roof.get("bound"), peak=roof.get("peak"), unit=roof.get("unit"),
                             achieved=None, frac=None, traffic=None)
     parity = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         try:
             parity = parity_leg(m, fn, clip_wave(4242), src, tgt, neg)
             log(f"parity vs the CPU oracle: {parity}")
@@ -516,7 +562,7 @@ def main():
         except Exception as e:
             log(f"parity leg failed: {e!r}")
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # many-core hosts (the MI355X box has 256) make torch's CPU kernels slower, not faster, on these
         # small tensors: use at most 32 threads and report that number as `cores`
         try:
@@ -524,7 +570,7 @@ def main():
         except Exception as e:          # the headline line must survive a failure of the reported-only baseline leg
             log(f"cpu_baseline failed: {e!r}")
     subs = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # BASELINE configs 3 (per-rank shape) / 4 / 5 as separate processes on this GPU: free this process's engines first
         pipe = None
         m._editors.clear()
@@ -883,7 +929,7 @@ def sub_benchmarks(elapsed_s):
     one JSON line; a failure or timeout is recorded, never fatal."""
     py, env = sys.executable, dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     jobs = [("config3_per_rank", [py, os.path.join(ROOT, "bench.py"), "--clips-per-gpu", "8", "--steps", "1", "--warmup",
-                                  "1", "--no-extras", "--no-cpu-baseline", "--no-batched"], 240),
+                                  "1", "--full", "--no-extras", "--no-cpu-baseline", "--no-batched"], 240),
             ("config4_pc_extract_apply", [py, os.path.join(ROOT, "tools", "bench_config4.py")], 300),
             ("config5_stable_audio", [py, os.path.join(ROOT, "tools", "bench_stable_audio.py"), "--steps", "1",
                                            "--warmup", "1"], 300),

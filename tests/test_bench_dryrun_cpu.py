@@ -1,6 +1,7 @@
 """bench.py's control flow executed on CPU with every GPU-facing piece mocked (model, engines, streams): guards the
 driver-facing contract -- ONE JSON line with the required keys, both inversion schedules, the roofline and traffic
-legs, --clips-per-gpu -- against run-time errors that would otherwise only show up on the GPU box."""
+legs (under --full), --clips-per-gpu, the plain run's lean path and --dump-outputs -- against run-time errors that would
+otherwise only show up on the GPU box."""
 import contextlib
 import io
 import json
@@ -152,22 +153,24 @@ class _Pipe:
         return dict(plan=self.plan, clips_in_flight=self.clips_in_flight, edit_cus=self.edit_cus)
 
 
-def _run(argv, batches, extra_patches=()):
+def _run(argv, batches, extra_patches=(), pipe=None, edit_clip=None):
     from audioeditingcode_amd import pipeline
     with contextlib.ExitStack() as stack:
         for pt in extra_patches:
             stack.enter_context(pt)
-        stack.enter_context(mock.patch.object(pipeline, "ClipPipeline", _Pipe))
-        return _run_inner(argv, batches)
+        stack.enter_context(mock.patch.object(pipeline, "ClipPipeline", pipe or _Pipe))
+        return _run_inner(argv, batches, edit_clip)
 
 
-def _run_inner(argv, batches):
+def _run_inner(argv, batches, edit_clip=None):
+    if edit_clip is None:
+        edit_clip = lambda m, x0, *a, **k: (None, None, torch.ones(1, 8, 256, 16))          # noqa: E731
     with mock.patch.object(sys, "argv", ["bench.py", *argv]), mock.patch("torch.cuda.set_device"), \
             mock.patch("torch.cuda.synchronize"), mock.patch("torch.cuda.Stream", _Stream), \
             mock.patch("torch.cuda.stream", _stream_ctx), mock.patch("torch.cuda.Event", _Event), \
             mock.patch.object(models, "load_model", lambda *a, **k: _Model(batches)), \
             mock.patch.object(bench, "check_fractions", lambda roof: None), \
-            mock.patch.object(main_run, "edit_clip", lambda m, x0, *a, **k: (None, None, torch.ones(1, 8, 256, 16))), \
+            mock.patch.object(main_run, "edit_clip", edit_clip), \
             mock.patch("audioeditingcode_amd.weights.random_state_dict", lambda *a, **k: {}), \
             mock.patch("torch.Tensor.to", lambda self, *a, **k: self), mock.patch("torch.device", lambda *a, **k: "cpu"):
         buf = io.StringIO()
@@ -183,9 +186,9 @@ REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 
 def test_default_line_has_the_contract_keys():
-    """Default mode: the two-stage partition pipeline + the two one-clip-at-a-time legs + the roofline measured per stage."""
+    """--full, default plan: the two-stage partition pipeline + the two one-clip-at-a-time legs + the roofline measured per stage."""
     _Pipe.made.clear()
-    out = _run(["--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-extras", "--group", "20", "--edit-cus", "96",
+    out = _run(["--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extras", "--group", "20", "--edit-cus", "96",
                 "--edit-lanes", "2", "--serial-clips", "2"], [2, 40])
     assert all(k in out for k in REQUIRED)
     assert out["n_gpus"] == 1 and out["steps"] == 4 and out["warmup"] == 2 and out["scaling"] == "weak"
@@ -215,14 +218,14 @@ def test_default_line_has_the_contract_keys():
 
 def test_serial_plan_single_clip_schedules_and_multi_clip_mode():
     _Pipe.made.clear()
-    out = _run(["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--plan", "serial", "--schedule",
+    out = _run(["--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras", "--plan", "serial", "--schedule",
                 "sequential", "--group", "20"], [2, 40])
     assert "value_single_clip_batched" in out and "reference order" in out["config"]["workload"]
     assert out["roofline"]["forward"]["unet_batch"] == 2
-    out = _run(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--plan", "serial", "--group", "20"],
+    out = _run(["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras", "--plan", "serial", "--group", "20"],
                [2, 40])
     assert out["roofline"]["forward"]["unet_batch"] == 40
-    out = _run(["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--clips-per-gpu", "2", "--group",
+    out = _run(["--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras", "--clips-per-gpu", "2", "--group",
                 "20", "--no-batched"], [4, 40])
     assert out["config"]["clips_per_gpu_per_step"] == 2 and out["config"]["gathered_latents"] == [[2, 8, 256, 16]]
     assert out["roofline"]["forward"]["unet_batch"] == 40
@@ -237,7 +240,7 @@ def test_extras_are_reported_and_never_fatal():
             return subprocess.CompletedProcess(cmd, 3, stdout="", stderr="boom")
         return subprocess.CompletedProcess(cmd, 0, stdout='noise\n{"metric": "m", "value": 2.5, "unit": "u", "roofline": '
                                                           '{"frac": 0.5, "by_batch": {}}}\n', stderr="")
-    out = _run(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--group", "20"], [2, 40],
+    out = _run(["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--group", "20"], [2, 40],
                extra_patches=[mock.patch.object(bench, "parity_leg", lambda *a, **k: dict(latent_rel_l2=1e-4)),
                               mock.patch.object(bench, "parity_fixture_leg", lambda *a, **k: dict(latent_rel_l2=2e-5)),
                               mock.patch.object(bench.subprocess, "run", fake_run)])
@@ -245,6 +248,67 @@ def test_extras_are_reported_and_never_fatal():
     assert out["config3_per_rank"]["value"] == 2.5 and out["config3_per_rank"]["roofline"] == {"frac": 0.5}
     assert out["config4_pc_extract_apply"]["failed"] == "rc=3"
     assert out["config5_stable_audio"]["value"] == 2.5
+
+
+def test_plain_run_times_the_steps_and_nothing_else():
+    """Without --full the run sets up, warms up, times the K steps and prints the line: no one-clip-at-a-time legs, phases,
+    roofline, parity, CPU baseline or sub-benchmarks; the headline keys keep their meaning, the reported-only ones are null."""
+    _Pipe.made.clear()
+    ran = []
+
+    def record(name):
+        return mock.patch.object(bench, name, lambda *a, **k: ran.append(name))
+    legs = ("roofline_leg", "clip_phases", "parity_leg", "parity_fixture_leg", "cpu_baseline", "sub_benchmarks")
+    out = _run(["--gpus", "1", "--steps", "5", "--warmup", "2"], [2, 200], extra_patches=[record(n) for n in legs])
+    assert ran == []
+    assert _Pipe.made[0].calls == [("warm_up", 1), ("edit_clips", 2), ("edit_clips", 5)]
+    assert all(k in out for k in REQUIRED)
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["n_gpus"] == 1 and out["higher_is_better"] is True
+    assert out["unit"] == "edited-clips/sec" and out["dtype"] == "f32" and abs(out["value"] * out["ms_per_step"] - 1e3) < 1e-6
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["parity"] is None
+    assert not any(k in out for k in ("value_reference_order", "value_single_clip_batched", "pipeline_vs_one_clip_at_a_time",
+                                      "config3_per_rank", "config4_pc_extract_apply", "config5_stable_audio"))
+
+
+class _SeededPipe(_Pipe):
+    """Clip i comes back as (waveform, original waveform, latent) filled with its seed."""
+
+    def edit_clips(self, items, *a, prepare=None, seeds=None, **k):
+        super().edit_clips(items, *a, prepare=prepare, seeds=seeds, **k)
+        return [(torch.full((1, 300), float(s)), torch.full((1, 300), -float(s)), torch.full((1, 8, 256, 16), float(s)))
+                for s in seeds]
+
+
+def _seeded_edit_clip(m, x0, *a, **k):
+    s = float(torch.initial_seed())                 # bench seeds every step with torch.manual_seed
+    return torch.full((1, 300), s), torch.full((1, 300), -s), torch.full((1, 8, 256, 16), s)
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: float32 DIR/<name>.npy of what the LAST timed step returned (clip K-1, seed 2000 + K - 1), in the
+    pipeline, in the one-clip-at-a-time plan and with several clips per step (the step returns their latents)."""
+    import numpy as np
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    d = str(tmp_path / "pipeline")
+    _run(["--steps", "3", "--warmup", "1", "--dump-outputs", d], [2, 200], pipe=_SeededPipe)
+    got = load(d)
+    assert set(got) == {"edited_waveform", "original_waveform", "edited_latent"}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["edited_latent"].shape == (1, 8, 256, 16) and (got["edited_latent"] == 2002).all()
+    assert (got["edited_waveform"] == 2002).all() and (got["original_waveform"] == -2002).all()
+
+    d = str(tmp_path / "serial")
+    _run(["--steps", "2", "--warmup", "1", "--plan", "serial", "--dump-outputs", d], [2, 200], edit_clip=_seeded_edit_clip)
+    got = load(d)
+    assert set(got) == {"edited_waveform", "original_waveform", "edited_latent"} and (got["edited_latent"] == 2001).all()
+
+    d = str(tmp_path / "clips2")
+    _run(["--steps", "1", "--warmup", "1", "--clips-per-gpu", "2", "--group", "20", "--dump-outputs", d], [4, 40])
+    got = load(d)
+    assert set(got) == {"edited_latent"} and got["edited_latent"].shape == (2, 8, 256, 16)
+    assert got["edited_latent"].dtype == np.float32
 
 
 def test_roofline_fraction_check_refuses_fractions_above_their_own_roof():
