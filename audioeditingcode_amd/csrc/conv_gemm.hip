@@ -566,9 +566,10 @@ int cg_fill_params(const aed_op* op, CGParams& p, int bkt) {
         AED_REQUIRE(p.A2 && p.C1 % 64 == 0 && p.C1 < p.Cin && p.lda2 % 4 == 0 && ((uintptr_t)p.A2 % 16) == 0 &&
                         (long long)(p.M / p.rpb) * p.a_bs2 + (long long)p.IH * p.IW * p.lda2 < (1LL << 31),
                     "conv_gemm: bad two-source split C1=%d of Cin=%d", p.C1, p.Cin);
+    // (o_len >= OH*OW: the GEGLU epilogues store every row q of a batch item at out_bs * b + q -- they never drop rows)
     if (p.geglu)
         AED_REQUIRE(p.ksplit == 1 && p.N % 64 == 0 && !p.res && p.out_act == 0 && p.accumulate == 0 && p.o_mul == 1 &&
-                        p.o_add == 0 && (p.ln_mode || !p.rowvec),
+                        p.o_add == 0 && p.o_len >= p.rpb && (p.ln_mode || !p.rowvec),
                     "conv_gemm: the GEGLU epilogue needs an unsplit GEMM with packed N %% 64 == 0 and a plain epilogue");
     return 0;
 }
