@@ -20,7 +20,7 @@
 // work of 24 bf16 MFMAs (6 x 4 k-blocks) of the split kernel -- the kernel is bound by the loader's VALU work, not by the matrix
 // pipe (pre-quantised weights would halve that; left for a follow-up).  LDS row = 64 B of fp8 + 16 B pad; scales sit beside
 // the rows as one dword per (row, k block).  Two LDS stages, one barrier per 64-k chunk, one further chunk in flight in registers.
-// Epilogue = conv_gemm_x6.hip's (the C/D layout of the 32x32 MFMAs does not depend on the input format).
+// Epilogue: cg_epilogue.h (the C/D layout of the 32x32 MFMAs does not depend on the input format).
 #include "cg_params.h"
 
 typedef int f8x32 __attribute__((ext_vector_type(8)));          // 32 fp8 = one lane's A / B operand of a 32x32x64 MFMA
@@ -301,146 +301,8 @@ __global__ __launch_bounds__(64 * WROWS * WCOLS, 2) void conv_gemm_f8_kernel(CGP
         cur ^= 1;
     }
 
-    // ---- fused LayerNorm: per-row statistics (the loader threads of a row are TPR adjacent lanes)
     float* ln_stat = reinterpret_cast<float*>(lds);      // [BM][2] (mean, rstd); the operand stages are dead
-    if (p.ln_mode) {
-#pragma unroll
-        for (int q = 0; q < PA; ++q) {
-            float s1 = ln_s1[q], s2 = ln_s2[q];
-#pragma unroll
-            for (int o = TPR / 2; o > 0; o >>= 1) {
-                s1 += __shfl_xor(s1, o, 64);
-                s2 += __shfl_xor(s2, o, 64);
-            }
-            if (lq == 0) {
-                const float mean = s1 / (float)p.K;
-                const float var = fmaxf(s2 / (float)p.K - mean * mean, 0.f);
-                ln_stat[2 * (lrow + RPP * q)] = mean;
-                ln_stat[2 * (lrow + RPP * q) + 1] = 1.0f / sqrtf(var + p.ln_eps);
-            }
-        }
-        __syncthreads();
-    }
-
-    // ---- epilogue (conv_gemm_x6.hip's): acc[a][b][r] = C[row (r&3) + 8*(r>>2) + 4*fh][col fi] of a 32x32 tile
-    if constexpr (TN % 2 == 0) {
-        if (p.geglu) {          // W rows packed [32 value | 32 gate] per 32 output features
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; b += 2) {
-                    const int nv = n0 + wc * WN + b * 32 + fi, ng = nv + 32;
-                    const int mbase = m0 + wr * WM + a * 32 + 4 * fh;
-                    if (ng >= p.N) continue;
-                    const float bv = p.bias ? p.bias[nv] : 0.f, bg = p.bias ? p.bias[ng] : 0.f;
-                    const float sv = p.ln_mode ? p.rowvec[nv] : 0.f, sg = p.ln_mode ? p.rowvec[ng] : 0.f;
-                    const int nf = ((n0 + wc * WN + b * 32) >> 1) + fi;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int dm = (r & 3) + 8 * (r >> 2);
-                        const int m = mbase + dm;
-                        float val = acc[a][b][r], gate = acc[a][b + 1][r];
-                        if (p.ln_mode) {
-                            const int lr = wr * WM + a * 32 + 4 * fh + dm;
-                            const float mean = ln_stat[2 * lr], rstd = ln_stat[2 * lr + 1];
-                            val = rstd * (val - mean * sv);
-                            gate = rstd * (gate - mean * sg);
-                        }
-                        val += bv;
-                        gate += bg;
-                        if (m < p.M) {
-                            const int bb = m / p.rpb;
-                            const unsigned row = (unsigned)bb * (unsigned)p.out_bs + (unsigned)(m - bb * p.rpb);
-                            p.C[row * (unsigned)p.ldc + nf] = val * glu_gate(gate, p.geglu);
-                        }
-                    }
-                }
-            return;
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) {
-            const int n = n0 + wc * WN + b * 32 + fi;
-            const int mbase = m0 + wr * WM + a * 32 + 4 * fh;
-            if (n >= p.N) continue;
-            if (p.ksplit > 1) {
-                float* wsp = p.ws + ((size_t)blockIdx.z * p.M + mbase) * p.N + n;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int dm = (r & 3) + 8 * (r >> 2);
-                    if (mbase + dm < p.M) wsp[(unsigned)dm * (unsigned)p.N] = acc[a][b][r];
-                }
-                continue;
-            }
-            const float bias_v = p.bias ? p.bias[n] : 0.f;
-            unsigned rows[16];
-            bool ok[16];
-            {
-                const int mb = min(mbase, p.M - 1);
-                const int b0 = mb / p.rpb;
-                const int q0 = mb - b0 * p.rpb;
-                const int bmax = (p.M - 1) / p.rpb;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int dm = (r & 3) + 8 * (r >> 2);
-                    int bb, q;
-                    if (p.rpb >= 32) {                 // at most one batch-item wrap inside a 32-row tile
-                        q = q0 + dm;
-                        const bool wrap = q >= p.rpb;
-                        bb = wrap ? b0 + 1 : b0;
-                        q = wrap ? q - p.rpb : q;
-                    } else {
-                        const int mm = min(mbase + dm, p.M - 1);
-                        bb = mm / p.rpb;
-                        q = mm - bb * p.rpb;
-                    }
-                    const int o = q * p.o_mul + p.o_add;
-                    ok[r] = (mbase + dm) < p.M && (unsigned)o < (unsigned)p.o_len;
-                    rows[r] = (unsigned)min(bb, bmax) * (unsigned)p.out_bs + (unsigned)min(max(o, 0), p.o_len - 1);
-                }
-            }
-            float val[16];
-            if (p.ln_mode) {
-                const float sn = p.rowvec[n];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int lr = wr * WM + a * 32 + 4 * fh + (r & 3) + 8 * (r >> 2);
-                    val[r] = ln_stat[2 * lr + 1] * (acc[a][b][r] - ln_stat[2 * lr] * sn) + bias_v;
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) val[r] = acc[a][b][r] + bias_v;
-            }
-            if (p.rowvec && !p.ln_mode) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    val[r] += p.rowvec[(rows[r] / (unsigned)p.out_bs) * (unsigned)p.ld_rv + n];
-            }
-            if (p.res) {
-                float rv[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) rv[r] = p.res[rows[r] * (unsigned)p.ldr + n];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) val[r] += rv[r];
-            }
-            if (p.out_act != AED_ACT_NONE) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) val[r] = aed_apply_act(val[r], p.out_act, p.out_p);
-            }
-            if (p.accumulate) {
-                float pv[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) pv[r] = p.C[rows[r] * (unsigned)p.ldc + n];
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    val[r] = (p.accumulate == 1) ? val[r] + pv[r] : (pv[r] + val[r]) / p.out_div;
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (ok[r]) p.C[rows[r] * (unsigned)p.ldc + n] = val[r];
-        }
+#include "cg_epilogue.h"
 }
 
 template <int BM, int BN, int WR, int WC>

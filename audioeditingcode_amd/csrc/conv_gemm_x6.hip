@@ -2,7 +2,7 @@
 //
 // The product's arithmetic for the LDS-staged GEMMs since round 4 (built in round 3): selected per op by flag bit 2 of an
 // AED_OP_CONV_GEMM record (include/aed.h); tapes built under tape.arith_mode("bf16x6") -- every U-Net / DiT / codec engine by
-// default -- set it.  Same record, same operands, same epilogue as conv_gemm.hip -- only the contraction differs.
+// default -- set it.  Same record, same operands, same epilogue (cg_epilogue.h) as conv_gemm.hip -- only the contraction differs.
 //
 // Why: the fp32-input MFMA (v_mfma_f32_32x32x2_f32) runs at the fp32 VECTOR rate, 1/16 of the bf16 MFMA
 // (MI355X_MICROARCH.md: 157 TF vs 2.5 PF).  An fp32 value is exactly the sum of three bf16 values (24 significand bits
@@ -22,7 +22,7 @@
 // writing the LDS stage.  LDS row = [hi 16 k | mid 16 k | lo 16 k | 16 B pad] = 112 B: the fragment read of one piece is
 // one ds_read_b128 per lane (8 consecutive k), conflict-free with this stride (28 dwords: the 16 rows of a b128 lane
 // group land on 16 distinct 4-bank windows).  A and W use the same k -> (lane half, element) map, so the result does not
-// depend on the instruction's internal k order; the C/D map is the one of the fp32 32x32 MFMA (conv_gemm.hip's epilogue).
+// depend on the instruction's internal k order; the C/D map is the one of the fp32 32x32 MFMA (cg_epilogue.h).
 //
 // Pipeline (as conv_gemm.hip): two LDS stages, chunk k+1 is split + written to the other stage while the MFMAs of
 // chunk k run, one barrier per chunk, DEPTH further chunks in flight in registers.  A chunk is 16 k = one bf16 k-block.
@@ -354,221 +354,8 @@ __global__ __launch_bounds__(64 * WROWS * WCOLS, 2) void conv_gemm_x6_kernel(CGP
         }
     }
 
-    // ---- fused LayerNorm: per-row statistics (the loader threads of a row are TPR adjacent lanes)
     float* ln_stat = reinterpret_cast<float*>(lds);      // [BM][2] (mean, rstd); the operand stages are dead
-    if (p.ln_mode) {
-#pragma unroll
-        for (int q = 0; q < PA; ++q) {
-            float s1 = ln_s1[q], s2 = ln_s2[q];
-#pragma unroll
-            for (int o = TPR / 2; o > 0; o >>= 1) {
-                s1 += __shfl_xor(s1, o, 64);
-                s2 += __shfl_xor(s2, o, 64);
-            }
-            if (lq == 0) {
-                const float mean = s1 / (float)p.K;
-                const float var = fmaxf(s2 / (float)p.K - mean * mean, 0.f);
-                ln_stat[2 * (lrow + RPP * q)] = mean;
-                ln_stat[2 * (lrow + RPP * q) + 1] = 1.0f / sqrtf(var + p.ln_eps);
-            }
-        }
-        __syncthreads();
-    }
-
-    // ---- epilogue (the semantics of conv_gemm.hip's): acc[a][b][r] = C[row (r&3) + 8*(r>>2) + 4*fh][col fi] of a 32x32 tile
-    if constexpr (TN % 2 == 0) {
-        if (p.geglu) {          // W rows packed [32 value | 32 gate] per 32 output features
-            const bool rows_are_m = p.out_bs == p.rpb;      // (every FF1 of the engines: output row = m, as in the simple-rows epilogue)
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; b += 2) {
-                    const int nv = n0 + wc * WN + b * 32 + fi, ng = nv + 32;
-                    const int mbase = m0 + wr * WM + a * 32 + 4 * fh;
-                    if (ng >= p.N) continue;
-                    const float bv = p.bias ? p.bias[nv] : 0.f, bg = p.bias ? p.bias[ng] : 0.f;
-                    const float sv = p.ln_mode ? p.rowvec[nv] : 0.f, sg = p.ln_mode ? p.rowvec[ng] : 0.f;
-                    const int nf = ((n0 + wc * WN + b * 32) >> 1) + fi;
-                    float out[16];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float val = acc[a][b][r], gate = acc[a][b + 1][r];
-                        if (p.ln_mode) {
-                            const int lr = wr * WM + a * 32 + 4 * fh + (r & 3) + 8 * (r >> 2);
-                            const float mean = ln_stat[2 * lr], rstd = ln_stat[2 * lr + 1];
-                            val = rstd * (val - mean * sv);
-                            gate = rstd * (gate - mean * sg);
-                        }
-                        val += bv;
-                        gate += bg;
-                        out[r] = val * glu_gate(gate, p.geglu);
-                    }
-                    if (rows_are_m) {
-                        float* cp = p.C + nf;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int m = mbase + (r & 3) + 8 * (r >> 2);
-                            if (m < p.M) cp[(unsigned)m * (unsigned)p.ldc] = out[r];
-                        }
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int m = mbase + (r & 3) + 8 * (r >> 2);
-                            if (m < p.M) {
-                                const int bb = m / p.rpb;
-                                const unsigned row = (unsigned)bb * (unsigned)p.out_bs + (unsigned)(m - bb * p.rpb);
-                                p.C[row * (unsigned)p.ldc + nf] = out[r];
-                            }
-                        }
-                    }
-                }
-            return;
-        }
-    }
-    // ---- simple rows (round 6): output row = m (every Linear and stride-1 convolution of the U-Net / DiT engines: no row scatter, no
-    // accumulate mode).  The general epilogue below spends ~30 instructions per output on row arithmetic that is the identity here;
-    // at the batch-200 forward's short-K Linears (K = 256 / 384: 16-24 chunks) that was a third of a tile's time
-    // (profiles/r06_short_k.md).  Same operations on the values, in the same order: bit-identical.
-    if (p.ksplit <= 1 && p.o_mul == 1 && p.o_add == 0 && p.out_bs == p.rpb && p.o_len == p.rpb && p.accumulate == 0 && !(p.diag & 1)) {
-        const bool has_rv = p.rowvec != nullptr && !p.ln_mode;
-        const int bmax = (p.M - 1) / p.rpb;
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int b = 0; b < TN; ++b) {
-                const int n = n0 + wc * WN + b * 32 + fi;
-                const int mbase = m0 + wr * WM + a * 32 + 4 * fh;
-                if (n >= p.N) continue;
-                const float bias_v = p.bias ? p.bias[n] : 0.f;
-                float val[16], rv[16];
-                if (p.res) {                // requested first: in flight while the values are finished
-                    const float* rp = p.res + n;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        rv[r] = rp[(unsigned)min(mbase + (r & 3) + 8 * (r >> 2), p.M - 1) * (unsigned)p.ldr];
-                }
-                if (p.ln_mode) {
-                    const float sn = p.rowvec[n];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int lr = wr * WM + a * 32 + 4 * fh + (r & 3) + 8 * (r >> 2);
-                        val[r] = ln_stat[2 * lr + 1] * (acc[a][b][r] - ln_stat[2 * lr] * sn) + bias_v;
-                    }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) val[r] = acc[a][b][r] + bias_v;
-                }
-                if (has_rv) {               // per-batch-item row vector (the resnets' time-embedding row)
-                    const int mb = min(mbase, p.M - 1), b0 = mb / p.rpb, q0 = mb - b0 * p.rpb;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int dm = (r & 3) + 8 * (r >> 2);
-                        int bb;
-                        if (p.rpb >= 32) bb = (q0 + dm >= p.rpb) ? b0 + 1 : b0;
-                        else bb = min(mbase + dm, p.M - 1) / p.rpb;
-                        val[r] += p.rowvec[(unsigned)min(bb, bmax) * (unsigned)p.ld_rv + n];
-                    }
-                }
-                if (p.res) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) val[r] += rv[r];
-                }
-                if (p.out_act != AED_ACT_NONE) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) val[r] = aed_apply_act(val[r], p.out_act, p.out_p);
-                }
-                float* cp = p.C + n;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = mbase + (r & 3) + 8 * (r >> 2);
-                    if (m < p.M) cp[(unsigned)m * (unsigned)p.ldc] = val[r];
-                }
-            }
-        return;
-    }
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b) {
-            const int n = n0 + wc * WN + b * 32 + fi;
-            const int mbase = m0 + wr * WM + a * 32 + 4 * fh;
-            if (n >= p.N) continue;
-            if (p.ksplit > 1) {
-                float* wsp = p.ws + ((size_t)bz * p.M + mbase) * p.N + n;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int dm = (r & 3) + 8 * (r >> 2);
-                    if (mbase + dm < p.M) wsp[(unsigned)dm * (unsigned)p.N] = acc[a][b][r];
-                }
-                continue;
-            }
-            const float bias_v = p.bias ? p.bias[n] : 0.f;
-            unsigned rows[16];
-            bool ok[16];
-            {
-                const int mb = min(mbase, p.M - 1);
-                const int b0 = mb / p.rpb;
-                const int q0 = mb - b0 * p.rpb;
-                const int bmax = (p.M - 1) / p.rpb;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int dm = (r & 3) + 8 * (r >> 2);
-                    int bb, q;
-                    if (p.rpb >= 32) {                 // at most one batch-item wrap inside a 32-row tile
-                        q = q0 + dm;
-                        const bool wrap = q >= p.rpb;
-                        bb = wrap ? b0 + 1 : b0;
-                        q = wrap ? q - p.rpb : q;
-                    } else {
-                        const int mm = min(mbase + dm, p.M - 1);
-                        bb = mm / p.rpb;
-                        q = mm - bb * p.rpb;
-                    }
-                    const int o = q * p.o_mul + p.o_add;
-                    ok[r] = (mbase + dm) < p.M && (unsigned)o < (unsigned)p.o_len;
-                    rows[r] = (unsigned)min(bb, bmax) * (unsigned)p.out_bs + (unsigned)min(max(o, 0), p.o_len - 1);
-                }
-            }
-            float val[16];
-            if (p.ln_mode) {
-                const float sn = p.rowvec[n];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int lr = wr * WM + a * 32 + 4 * fh + (r & 3) + 8 * (r >> 2);
-                    val[r] = ln_stat[2 * lr + 1] * (acc[a][b][r] - ln_stat[2 * lr] * sn) + bias_v;
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) val[r] = acc[a][b][r] + bias_v;
-            }
-            if (p.rowvec && !p.ln_mode) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    val[r] += p.rowvec[(rows[r] / (unsigned)p.out_bs) * (unsigned)p.ld_rv + n];
-            }
-            if (p.res) {
-                float rv[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) rv[r] = p.res[rows[r] * (unsigned)p.ldr + n];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) val[r] += rv[r];
-            }
-            if (p.out_act != AED_ACT_NONE) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) val[r] = aed_apply_act(val[r], p.out_act, p.out_p);
-            }
-            if (p.accumulate) {
-                float pv[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) pv[r] = p.C[rows[r] * (unsigned)p.ldc + n];
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    val[r] = (p.accumulate == 1) ? val[r] + pv[r] : (pv[r] + val[r]) / p.out_div;
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (ok[r]) p.C[rows[r] * (unsigned)p.ldc + n] = val[r];
-        }
+#include "cg_epilogue.h"
 }
 
 template <int BM, int BN, int WR, int WC, int DEPTH, bool DIAG, int BK = X6_BK>

@@ -12,7 +12,7 @@ item ends inside a 32-row sub-tile.  Per record:
   * the split kernel really ran (its `fits` holds and its output differs from the fp32 kernel's);
   * C is pre-filled with NaN and has a row pitch ldc > N with sentinel padding: every due element is written, no pad is touched;
   * ksplit 1: the general epilogue (flag 0x8000), the n-fastest order (1024), forced group heights (bits 11-13) and every
-    CU-budget value (bits 16-17) give bitwise the default launch's output;
+    CU-budget value (bits 16-17) give bitwise the default launch's output; so does the fp32 kernel's general epilogue;
   * the three-term diagnostic (flag 16; tiles 1 / 8 with a plain A) FAILS the bounds: the test can see one missing piece product.
 Then production-size records on tiles 1, 8 and 9 (FF1 + LayerNorm + GEGLU at batch 200 among them) whose tile groups end in a
 partial group, NaN-checked on the device and compared with fp64 on sampled row panels."""
@@ -307,6 +307,10 @@ def bit_identities(rec, y6, label):
     for fl in variants:
         yv = rec.launch(fl)
         assert torch.equal(yv.view(torch.int32), y6.view(torch.int32)), f"{label}: flags {fl:#x} differ from the default launch"
+    # the fp32 kernel shares the epilogue (cg_epilogue.h): its general path too gives its default launch's output
+    y32 = rec.fp32()
+    y32g = rec.launch((rec.flags & ~ARITH_BITS & ~4) | 0x8000, 1 if tile in (8, 9) else tile)
+    assert torch.equal(y32g.view(torch.int32), y32.view(torch.int32)), f"{label}: fp32 kernel, flag 0x8000 differs"
 
 
 def test_shipped_split_bf16_record_classes_against_fp64():
