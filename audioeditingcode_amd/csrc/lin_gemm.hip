@@ -99,8 +99,8 @@ __global__ __launch_bounds__(64 * NW) void lin_gemm_kernel(CGParams p) {
             aoff2[j] = (unsigned)mm * (unsigned)p.lda2 + lseg;
         }
     }
-    // batch item of this tile's rows (per-batch weights / vectors; a tile never straddles batch items there)
-    const int bt = (p.w_bs | p.vec_bs) ? min(m0, p.M - 1) / p.rpb : 0;
+    // batch item of this tile's rows (per-batch weights / vectors / key bias; a tile never straddles batch items there)
+    const int bt = (p.w_bs | p.vec_bs | p.sm_group) ? min(m0, p.M - 1) / p.rpb : 0;
     unsigned woff[PW];
 #pragma unroll
     for (int j = 0; j < PW; ++j) {
@@ -482,10 +482,18 @@ int launch_lin_gemm(const CGParams& p, int cfg, hipStream_t s) {
                     "lin_gemm: bad two-source split C1=%d of Cin=%d", p.C1, p.Cin);
     if (p.w_bs || p.vec_bs || p.sm_group)
         AED_REQUIRE(p.rpb % 64 == 0 && p.M % p.rpb == 0, "lin_gemm: per-batch operands need 64-row aligned batch items");
-    if (p.sm_group)
+    // the simple-rows epilogue's layout: output row = m, no per-batch row vector (ln_mode's row sum aside), no accumulate
+    const bool plain_rows = p.o_mul == 1 && p.o_add == 0 && p.out_bs == p.rpb && p.o_len == p.rpb && p.accumulate == 0 &&
+                            (!p.rowvec || p.ln_mode);
+    if (p.sm_group)     // (the softmax epilogue ends the record: no residual, row vector, activation or row scatter)
         AED_REQUIRE((p.sm_group == 8 || p.sm_group == 16 || p.sm_group == 32) && p.N % 32 == 0 && !p.res && !p.geglu &&
-                        p.o_mul == 1 && p.o_add == 0 && p.out_bs == p.rpb && p.accumulate == 0,
+                        p.out_act == 0 && plain_rows,
                     "lin_gemm: grouped softmax needs groups of 8/16/32 columns, N %% 32 == 0 and a plain row layout");
+    // bias and the LayerNorm row sum at b * vec_bs + n * vec_ld are read so by the simple-rows, GEGLU and softmax epilogues
+    // only; the general one (store_out) reads bias[n]
+    if (p.vec_ld != 1 || p.vec_bs)
+        AED_REQUIRE(plain_rows, "lin_gemm: strided / per-batch bias vectors (vec_ld=%d vec_bs=%d) need a plain row layout",
+                    p.vec_ld, p.vec_bs);
     if (p.geglu)
         AED_REQUIRE(p.N % 64 == 0 && (cfg == 13 || cfg == 14 || cfg == 15 || cfg == 17) && !p.res && p.out_act == 0 &&
                         p.o_mul == 1 && p.o_add == 0 && (p.ln_mode || !p.rowvec),

@@ -212,6 +212,146 @@ def test_reference_scale_bounds_an_fp32_evaluation():
     assert float(err.max()) < 64 * 2.0 ** -24, float(err.max())
 
 
+# ---- per-batch operands and the grouped softmax (the folded cross-attention, unet._folded_cross_attention) ----------------
+def _folded_scores_case(group, B=3, rpb=5, K=48, heads=2, seed=0):
+    """A scores record of the folded cross-attention's form: per-batch W (with a gap between the items), the LayerNorm fold's
+    (rowsum, bias) pairs interleaved per (batch item, column) as unet.py lays them out (vec_ld 2), a key bias per batch item:
+    batch 0 with -10000 masked keys, batch 1 with one -1e30 key, batch 2 fully masked."""
+    g = _g(seed + group)
+    N = heads * group
+    w_bs = N * K + 16
+    x = torch.randn(B * rpb, K, generator=g) * 2 + 0.5
+    Wb = torch.randn(B, N, K, generator=g) / K ** 0.5
+    bias = torch.randn(B, N, generator=g) * 0.3
+    Wflat = torch.full(((B - 1) * w_bs + N * K,), float("nan"))
+    for b in range(B):
+        Wflat[b * w_bs: b * w_bs + N * K] = Wb[b].reshape(-1)
+    gs = torch.stack([Wb.sum(2), bias], 2)                               # [B, N, 2]: (rowsum, bias) of every column
+    kb = torch.randn(B, group, generator=g) * 0.5
+    kb[0, 1::3] = -10000.0
+    kb[1, group // 2] = -1e30
+    kb[2:, :] = -10000.0
+    scale = 0.25
+    i = record(B=B, IH=rpb, IW=1, Cin=K, OH=rpb, OW=1, N=N, ln_mode=1, sm_group=group, w_bs=w_bs, vec_ld=2, vec_bs=2 * N)
+    f = [0.0, 0.0, 1.0, 1e-5, scale]
+    ops = dict(A=x.reshape(-1), W=Wflat, bias=gs.reshape(-1)[1:], rowvec=gs.reshape(-1), kbias=kb.reshape(-1))
+    return i, f, ops, (x, Wb, bias, kb, scale)
+
+
+def _softmax_expected(x, Wb, bias, kb, scale, group, rpb):
+    B, N, K = Wb.shape
+    ln = F.layer_norm(x, (K,), eps=1e-5).reshape(B, rpb, K)
+    z = (torch.einsum("bmk,bnk->bmn", ln, Wb) + bias[:, None, :]) * scale + kb.repeat(1, N // group)[:, None, :]
+    return torch.softmax(z.reshape(B, rpb, N // group, group), -1).reshape(B * rpb, N)
+
+
+@pytest.mark.parametrize("group", [8, 16, 32])
+def test_reference_grouped_softmax_with_per_batch_weights_and_interleaved_vectors(group):
+    i, f, ops, (x, Wb, bias, kb, scale) = _folded_scores_case(group)
+    out, sc, written = conv_gemm_ref(i, f, ops["A"], ops["W"], bias=ops["bias"], rowvec=ops["rowvec"], kbias=ops["kbias"])
+    N = i[1]
+    want = _softmax_expected(x, Wb, bias, kb, scale, group, 5)
+    torch.testing.assert_close(out.reshape(-1, N), want, rtol=1e-12, atol=1e-12)
+    assert bool(written.all()) and torch.isfinite(sc).all()
+    p = out.reshape(3, 5, N // group, group)
+    assert torch.allclose(p.sum(-1), torch.ones(()), atol=1e-12)
+    assert (p[1, :, :, group // 2] == 0).all()                                         # the -1e30 key
+    unmasked = _softmax_expected(x, Wb, bias, 0 * kb, scale, group, 5).reshape(3, 5, N // group, group)
+    torch.testing.assert_close(p[2], unmasked[2], rtol=1e-9, atol=1e-12)       # a fully masked group: the unmasked softmax
+
+
+@pytest.mark.parametrize("what", ["w_bs", "vec_ld", "vec_bs", "kbias", "sm_scale", "sm_group"])
+def test_reference_per_batch_fields_are_read_exactly(what):
+    """Each per-batch field moved by one element (or the key bias dropped) changes the interpreter's output: what the GPU tests
+    compare against depends on every one of them."""
+    group = 16
+    i, f, ops, _ = _folded_scores_case(group)
+    base, _, _ = conv_gemm_ref(i, f, ops["A"], ops["W"], bias=ops["bias"], rowvec=ops["rowvec"], kbias=ops["kbias"])
+    i2, f2, kb = list(i), list(f), ops["kbias"]
+    W = ops["W"]
+    if what == "w_bs":          # the later items' W one element earlier (the gap made NaN-free: the value changes)
+        W = torch.nan_to_num(W, nan=0.5)
+        i2[37] -= 1
+    elif what == "vec_ld":
+        i2[38], i2[39] = 1, i[39]
+    elif what == "vec_bs":
+        i2[39] -= 2
+    elif what == "kbias":
+        kb = None
+    elif what == "sm_scale":
+        f2[4] *= 1.001
+    else:
+        i2[36] = group // 2
+    got, _, _ = conv_gemm_ref(i2, f2, ops["A"], W, bias=ops["bias"], rowvec=ops["rowvec"], kbias=kb)
+    assert not torch.allclose(got, base, rtol=1e-6, atol=1e-9, equal_nan=True), what
+
+
+def test_reference_softmax_scale_bounds_an_fp32_evaluation():
+    """The grouped softmax's error scale bounds an fp32 evaluation in the kernel's order (fp32 product, LayerNorm fold, bias,
+    scale, key bias, max-subtracted exp, sum, division) within a small multiple of 2^-24, -10000 masked keys included."""
+    for group in (8, 16, 32):
+        i, f, ops, (x, Wb, bias, kb, scale) = _folded_scores_case(group, B=2, rpb=64, K=256, heads=4, seed=9)
+        kb[1, :] = torch.where(torch.arange(group) % 2 == 0, kb[1, :], torch.full((group,), -10000.0))
+        ops["kbias"] = kb.reshape(-1)
+        ref, sc, _ = conv_gemm_ref(i, f, ops["A"], ops["W"], bias=ops["bias"], rowvec=ops["rowvec"], kbias=ops["kbias"])
+        B, N, K = Wb.shape
+        x32 = x.float().reshape(B, 64, K)
+        mean = x32.mean(2, keepdim=True)
+        rstd = 1 / torch.sqrt((x32 * x32).mean(2, keepdim=True) - mean * mean + 1e-5)
+        acc = torch.einsum("bmk,bnk->bmn", x32, Wb.float())
+        z = (rstd * (acc - mean * Wb.float().sum(2)[:, None, :]) + bias.float()[:, None, :]) * scale
+        z = (z + kb.float().repeat(1, N // group)[:, None, :]).reshape(B, 64, N // group, group)
+        e = torch.exp(z - z.max(-1, keepdim=True).values)
+        y32 = (e / e.sum(-1, keepdim=True)).reshape(B * 64, N)
+        err = (y32.double() - ref.reshape(-1, N)).abs() / sc.reshape(-1, N).clamp_min(1e-300)
+        assert float(err.max()) < 64 * 2.0 ** -24, (group, float(err.max()))
+
+
+def test_reference_agrees_with_the_tape_interpreter_on_a_folded_cross_attention_pair():
+    """One folded cross-attention site of a CPU-laid-out engine (scores + softmax, then P . VO + bias + residual): the tape
+    interpreter (oracle/tape_interp.py, which the CPU suite runs engines with) and this interpreter give the same output."""
+    from audioeditingcode_amd import _lib as L, configs, weights
+    from audioeditingcode_amd.unet import UNetEngine
+    from oracle import tape_interp
+    torch.set_default_dtype(torch.float32)
+    fam = configs.tiny_family("audioldm2")
+    sd = weights.random_state_dict(weights.unet_param_shapes(fam["unet"]), seed=0)
+    eng = UNetEngine(fam["unet"], sd, "cpu", 2, 256, 16, ctx_len0=8, ctx_len1=16)
+    torch.set_default_dtype(torch.float64)
+    ops = [(o, mt["name"]) for o, mt in zip(eng.tape.ops, eng.tape.meta) if o.code == L.OP_CONV_GEMM]
+    k = next(n for n, (o, name) in enumerate(ops) if name.endswith("attn2.scores+softmax") and o.p[9])
+    pair = [ops[k][0], ops[k + 1][0]]
+    assert ops[k + 1][1].endswith("attn2.PV+to_out") and pair[1].p[0] == pair[0].p[3]
+    g = _g(3)
+    for n, o in enumerate(pair):
+        i = [int(v) for v in o.i]
+        M, N, K, lda, ldc, ldr = i[:6]
+        nb, rpb = M // (i[9] * i[10]), i[9] * i[10]
+        view = tape_interp._f32
+        sizes = {0: (nb - 1) * i[20] + rpb * lda, 1: (nb - 1) * i[37] + N * K, 4: M * ldr}
+        vlen = (nb - 1) * i[39] + (N - 1) * max(i[38], 1) + 1
+        sizes.update({2: vlen, 5: vlen + 1 if i[38] == 2 else vlen, 9: nb * i[36]})
+        for slot, ln in sizes.items():
+            if o.p[slot] and not (n == 1 and slot == 0):                # P is the first record's output
+                t = view(o.p[slot], ln)
+                t.copy_(torch.randn(ln, generator=g).float() * (0.2 if slot == 1 else 1.0))
+        if n == 0:      # a realistic prompt mask: the last keys of batch item 1 are padding
+            kb = view(o.p[9], nb * i[36])
+            kb.zero_()
+            kb[i[36] + i[36] // 2:] = -10000.0
+            gs = view(o.p[5], vlen + 1).reshape(-1)
+            W = view(o.p[1], sizes[1])
+            for b in range(nb):                                          # rowsum = sum_k W'[n, k] per batch item
+                gs[b * i[39]: b * i[39] + 2 * N: 2] = W[b * i[37]: b * i[37] + N * K].reshape(N, K).double().sum(1).float()
+        host = {s: view(o.p[s], ln).clone() for s, ln in sizes.items() if o.p[s]}
+        host[0] = view(o.p[0], sizes[0]).clone()
+        ref, _, written = conv_gemm_ref(i, [float(v) for v in o.f][:5], host[0], host[1], bias=host.get(2),
+                                        res=host.get(4), rowvec=host.get(5), kbias=host.get(9))
+        tape_interp.conv_gemm(o)
+        got = view(o.p[3], M * ldc).double()
+        torch.testing.assert_close(got[written], ref[written], rtol=2e-5, atol=2e-6)
+
+
 # ---- tile tables ----------------------------------------------------------------------------------------------------------
 X6_TILES = {1, 2, 3, 4, 8, 9}                 # tile codes of conv_gemm_x6.hip (table code = 100 + tile)
 FP32_TILES = {1, 2, 3, 4, 5, 6}               # conv_gemm.hip
