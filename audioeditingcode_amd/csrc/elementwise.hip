@@ -231,6 +231,18 @@ __global__ __launch_bounds__(256) void invert_step_kernel(StepParams p) {
     }
 }
 
+// x_{t-1} of reverse_step_with_custom_noise (models.py:119-158) in the reference's fp32 expression order; shared by the
+// one-edit and the K-variant step kernels so that both compute the same bits from the same inputs.
+__device__ __forceinline__ float reverse_update(float x, float eps, const float* z, size_t e, int v_pred, float c0,
+                                                float c1, float c2, float c3, float c4) {
+    float x0, dir;
+    if (!v_pred) { x0 = (x - c0 * eps) / c1; dir = eps; }
+    else { x0 = c1 * x - c0 * eps; dir = c1 * eps + c0 * x; }
+    float prev = c2 * x0 + c3 * dir;
+    if (z) prev = prev + c4 * z[e];
+    return prev;
+}
+
 __global__ __launch_bounds__(256) void reverse_step_kernel(StepParams p) {
     const int s = p.state ? p.state[0] * p.s_mul + p.s_off : p.s_imm;
     float c0, c1, c2, c3, c4;
@@ -241,14 +253,78 @@ __global__ __launch_bounds__(256) void reverse_step_kernel(StepParams p) {
     if (p.has_noise) z = (p.T > 0) ? p.zs + (size_t)(p.T - s - 1) * p.numel : p.zs;   // T := number of zs (Z); 0 => explicit z
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < p.numel; e += (size_t)gridDim.x * 256) {
         const float eps = cfg_combine(p, e);
-        const float x = xt[e];
-        float x0, dir;
-        if (!p.v_pred) { x0 = (x - c0 * eps) / c1; dir = eps; }
-        else { x0 = c1 * x - c0 * eps; dir = c1 * eps + c0 * x; }
-        float prev = c2 * x0 + c3 * dir;
-        if (z) prev = prev + c4 * z[e];
-        p.out[e] = prev;
+        p.out[e] = reverse_update(xt[e], eps, z, e, p.v_pred, c0, c1, c2, c3, c4);
     }
+}
+
+// ------------------------------------------------------------------------------------ K1 for K edits of one inversion
+// One reverse step of `a` edit variants of ONE inverted clip, all at the same timestep (EditEngine.edit_variants): the
+// variants are rows of cur [K][numel] (rows [0, a) are active), the U-Net's eps is [a uncond | a cond] x numel, each
+// variant has its own scalar guidance cfg[v] (device), and all of them read the ONE shared noise table zs [Z][numel].
+// Variant v computes exactly what reverse_step_kernel computes with P = 1 and cfg_scalar = cfg[v]: the same
+// cfg_combine scalar form u + g * (c - u) and the same reverse_update.  Plain grid-stride loop over element positions;
+// every thread reads z once and walks the a variants, whose loads are independent (bytes in flight at small numel).
+struct VariantStepParams {
+    const float* cur;      // x_t rows [a][numel]
+    float* out;            // x_{t-1} rows [a][numel] (may alias cur)
+    const float* zs;       // [Z][numel] device-indexed, or one explicit z [numel] (Z == 0); null -> no noise
+    const float* eps;      // [2a][numel]: rows [0, a) unconditional, [a, 2a) conditional
+    const float* cfg;      // [a]
+    const float* coef;     // device table [steps][8] or null -> c[] immediates
+    const int* state;      // device step counter or null -> s_imm
+    size_t numel;
+    int a, Z, s_imm, v_pred, s_mul, s_off;
+    float c[5];
+};
+
+__global__ __launch_bounds__(256) void reverse_step_variants_kernel(VariantStepParams p) {
+    const int s = p.state ? p.state[0] * p.s_mul + p.s_off : p.s_imm;
+    float c0, c1, c2, c3, c4;
+    if (p.coef) { const float* c = p.coef + (size_t)s * AED_COEF_STRIDE; c0 = c[0]; c1 = c[1]; c2 = c[2]; c3 = c[3]; c4 = c[4]; }
+    else { c0 = p.c[0]; c1 = p.c[1]; c2 = p.c[2]; c3 = p.c[3]; c4 = p.c[4]; }
+    const float* z = nullptr;
+    if (p.zs) z = (p.Z > 0) ? p.zs + (size_t)(p.Z - s - 1) * p.numel : p.zs;
+    const float* eps_c = p.eps + (size_t)p.a * p.numel;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < p.numel; e += (size_t)gridDim.x * 256) {
+        const float zz = z ? z[e] : 0.f;
+#pragma unroll 4
+        for (int v = 0; v < p.a; ++v) {
+            const size_t o = (size_t)v * p.numel + e;
+            const float u = p.eps[o];
+            const float eps = u + p.cfg[v] * (eps_c[o] - u);          // cfg_combine, P = 1
+            p.out[o] = reverse_update(p.cur[o], eps, z ? &zz : nullptr, 0, p.v_pred, c0, c1, c2, c3, c4);
+        }
+    }
+}
+
+static int launch_variants(const VariantStepParams& p, hipStream_t s, const char* what) {
+    AED_REQUIRE(p.cur && p.out && p.eps && p.cfg, "%s: null pointer", what);
+    AED_REQUIRE(p.a >= 1 && p.Z >= 0, "%s: bad variant count %d / Z %d", what, p.a, p.Z);
+    AED_REQUIRE(p.out == p.cur || p.out + (size_t)p.a * p.numel <= p.cur || p.cur + (size_t)p.a * p.numel <= p.out,
+                "%s: out must be cur or not overlap it", what);
+    if (p.numel == 0) return 0;
+    hipLaunchKernelGGL(reverse_step_variants_kernel, dim3(grid_for(p.numel)), dim3(256), 0, s, p);
+    AED_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// slots: p0=cur [K][numel] (rows [0, a) stepped)  p1=zs base | z | null (no noise)  p2=eps [2a][numel]  p4=cfg [a] (device)
+//        p5=coef table (nullable)  p6=state (nullable)  p7=out (null => in place into p0)
+//   i0,i1=numel lo/hi  i2=a  i3=Z (#zs; 0 => p1 is the explicit z)  i4=s_imm  i5=v_pred  i6=has_noise
+//   i7=s_mul i8=s_off (step = state*s_mul + s_off)   f1..f5 = c0..c4 immediates (used when p5 is null)
+int launch_reverse_step_variants(const aed_op* op, hipStream_t s) {
+    VariantStepParams p = {};
+    p.cur = (const float*)op->p[0];
+    p.zs = op->i[6] ? (const float*)op->p[1] : nullptr;
+    p.eps = (const float*)op->p[2]; p.cfg = (const float*)op->p[4];
+    p.coef = (const float*)op->p[5]; p.state = (const int*)op->p[6];
+    p.out = op->p[7] ? (float*)op->p[7] : (float*)op->p[0];
+    p.numel = (size_t)(uint32_t)op->i[0] | ((size_t)(uint32_t)op->i[1] << 32);
+    p.a = op->i[2]; p.Z = op->i[3]; p.s_imm = op->i[4]; p.v_pred = op->i[5];
+    p.s_mul = op->i[7] > 0 ? op->i[7] : 1; p.s_off = op->i[8];
+    for (int k = 0; k < 5; ++k) p.c[k] = op->f[1 + k];
+    AED_REQUIRE(!op->i[6] || op->p[1], "reverse_step_variants: noise requested but zs is null");
+    return launch_variants(p, s, "reverse_step_variants");
 }
 
 // slots (both): p0=xts base | xt   p1=zs base | z   p2=eps_u  p3=eps_c  p4=cfg  p5=coef table  p6=state  p7=out
@@ -317,6 +393,18 @@ extern "C" int aed_reverse_step_with_custom_noise(const float* xt, const float* 
     hipLaunchKernelGGL(reverse_step_kernel, dim3(grid_for(p.numel)), dim3(256), 0, (hipStream_t)stream, p);
     AED_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int aed_reverse_step_variants(const float* xt, const float* eps, const float* cfg, int n_variants,
+                                         const float* coef_host, int v_prediction, const float* z, float* prev_out,
+                                         int64_t numel, void* stream) {
+    VariantStepParams p = {};
+    p.s_mul = 1;
+    p.cur = xt; p.out = prev_out; p.zs = z; p.Z = 0; p.eps = eps; p.cfg = cfg; p.a = n_variants;
+    p.v_pred = v_prediction; p.numel = (size_t)numel;
+    AED_REQUIRE(coef_host && numel >= 0, "aed_reverse_step_variants: null coefficients or negative numel");
+    for (int k = 0; k < 5; ++k) p.c[k] = coef_host[k];
+    return launch_variants(p, (hipStream_t)stream, "aed_reverse_step_variants");
 }
 
 __global__ __launch_bounds__(256) void sample_xts_kernel(const float* __restrict__ x0, const float* __restrict__ noise,

@@ -56,6 +56,11 @@ class Conditioning:
         f = lambda t: None if t is None else t.repeat_interleave(n, 0) if t.shape[0] == 1 else t  # noqa: E731
         return Conditioning(f(self.ehs0), f(self.ehs1), f(self.mask0), f(self.mask1), f(self.class_labels))
 
+    def select(self, rows):
+        """The rows `rows` (a list of indices) of every tensor, in that order."""
+        f = lambda t: None if t is None else t[list(rows)]                                          # noqa: E731
+        return Conditioning(f(self.ehs0), f(self.ehs1), f(self.mask0), f(self.mask1), f(self.class_labels))
+
 
 def _pad_ctx(parts, L, attr_e, attr_m):
     """Stack per-group context tensors of different lengths into [R, L, d] + additive bias [R, L], on the device the
@@ -75,6 +80,68 @@ def _pad_ctx(parts, L, attr_e, attr_m):
     return torch.cat(es, 0), torch.cat(bs, 0)
 
 
+def variant_plan(tstarts, n_zs, max_variants=None):
+    """The segment plan of EditEngine.edit_variants.  Returns (order, segments): `order` lists the variants sorted by
+    tstart, largest first (stable: equal tstarts keep the caller's order); segment j covers the loop steps between the
+    j-th and the (j+1)-th distinct tstart with the prefix [0, a) of `order` active, dict(tstart, a, join=(lo, hi): the
+    sorted rows that start at this segment from xts[tstart], start: first loop step, steps).  Refuses an empty list, more
+    than `max_variants` and a tstart outside [1, n_zs] (n_zs: the noise maps the caller holds)."""
+    ts = [int(t) for t in tstarts]
+    if not ts:
+        raise ValueError("edit_variants: the list of variants is empty")
+    if max_variants is not None and len(ts) > max_variants:
+        raise ValueError(f"edit_variants: {len(ts)} variants in one call, at most {max_variants} "
+                         f"(variants.inversion_reverse_variants splits longer lists)")
+    for t in ts:
+        if not 1 <= t <= n_zs:
+            raise ValueError(f"edit_variants: tstart {t} outside [1, {n_zs}] (the number of noise maps zs holds)")
+    order = sorted(range(len(ts)), key=lambda v: -ts[v])
+    segs, i = [], 0
+    while i < len(order):
+        j = i
+        while j < len(order) and ts[order[j]] == ts[order[i]]:
+            j += 1
+        segs.append(dict(tstart=ts[order[i]], a=j, join=(i, j)))
+        i = j
+    for k, sg in enumerate(segs):
+        nxt = segs[k + 1]["tstart"] if k + 1 < len(segs) else 0
+        sg["start"], sg["steps"] = segs[0]["tstart"] - sg["tstart"], sg["tstart"] - nxt
+    return order, segs
+
+
+def variant_positions(order):
+    """The inverse of variant_plan's `order`: entry v is the sorted row that holds the caller's variant v."""
+    pos = [0] * len(order)
+    for i, v in enumerate(order):
+        pos[v] = i
+    return pos
+
+
+def variant_noise(eta_rows):
+    """Whether the edit loop adds the noise term (EditEngine._etas_in_loop_order output: a float or one value per step).
+    A per-step list that is zero at SOME steps only is refused: the reference skips `+ eta*sigma*z` there (models.py:152),
+    the fused step would multiply a possibly non-finite z by zero (inversion_reverse_process takes the literal path)."""
+    if isinstance(eta_rows, float):
+        return eta_rows > 0
+    if any(e == 0 for e in eta_rows) and any(e != 0 for e in eta_rows):
+        raise ValueError("edit_variants: a per-step eta list that is zero at some steps and non-zero at others is not "
+                         "supported by the device loop; use inversion_reverse_process per variant")
+    return any(e > 0 for e in eta_rows)
+
+
+def _variant_rows(cond, K, what):
+    """One one-row Conditioning per variant from a list of K, or from one Conditioning with K rows or 1 (shared) row."""
+    if isinstance(cond, (list, tuple)):
+        if len(cond) != K or any(c.rows != 1 for c in cond):
+            raise ValueError(f"edit_variants: {what} must be {K} one-row Conditioning objects")
+        return list(cond)
+    if cond.rows == 1:
+        return [cond] * K
+    if cond.rows == K:
+        return [cond.select([v]) for v in range(K)]
+    raise ValueError(f"edit_variants: {what} has {cond.rows} rows for {K} variants")
+
+
 class LoopPlumbing:
     """What the device-resident loop engines share (this module's EditEngine, stable_audio.StableAudioEditEngine): an LRU
     of loop plans (persistent buffers + tapes + one instantiated hipGraph per loop shape) and the graph runner.
@@ -82,11 +149,13 @@ class LoopPlumbing:
 
     def _drop_plan(self, key):
         old = self._plans.pop(key)
-        g = old.get("graph")
-        if g is not None:
-            if self.stream is not None:
-                torch.cuda.synchronize(self.device)       # the graph may be in flight on a pipeline lane, not only on self.stream
-            L.check(L.lib().aed_graph_destroy(g), "aed_graph_destroy")
+        # a plan holds one graph, or one per loop segment (EditEngine.edit_variants)
+        graphs = [p.get("graph") for p in [old] + list(old.get("segs", ()))]
+        if any(g is not None for g in graphs) and self.stream is not None:
+            torch.cuda.synchronize(self.device)           # the graph may be in flight on a pipeline lane, not only on self.stream
+        for g in graphs:
+            if g is not None:
+                L.check(L.lib().aed_graph_destroy(g), "aed_graph_destroy")
 
     def _get_plan(self, key):
         """LRU lookup of a loop plan; on a miss makes room for the plan the caller is about to build."""
@@ -508,6 +577,87 @@ class EditEngine(LoopPlumbing):
             post.run()
         self._run_graph(body, Z if n_steps is None else max(0, min(int(n_steps), Z)), use_graph, plan)
         return cur.clone()
+
+    # ------------------------------------------------------------------ K edits of one inversion
+    MAX_VARIANTS = 16       # variants per edit_variants call (U-Net batch <= 32); variants.inversion_reverse_variants chunks
+
+    @torch.inference_mode()
+    def edit_variants(self, xts, zs, tstarts, cond_tgt, cond_neg, cfg_tars, eta=1.0, use_graph=True):
+        """K edits of ONE inverted clip in one device-resident loop.  Variant v is `edit(xts, zs, tstarts[v], cond_tgt[v],
+        cond_neg[v], [cfg_tars[v]], eta)`; all of them share the trajectory xts [T+1, 1, H, W, C] and the noise maps
+        zs [>= max(tstarts), 1, H, W, C] (channels-last, as invert() returns them).  cond_tgt / cond_neg: a list of K
+        one-row Conditioning objects, or one Conditioning with K rows or 1 row (shared).  eta: one float, or the
+        reference's per-step list (indexed by noise-map number) shared by every variant.
+
+        The variants run sorted by tstart, largest first: the loop walks the max(tstart) steps in segments between the
+        distinct tstarts, and in each segment the active variants are a prefix of the sorted list whose U-Net batch is
+        [a unconditional | a conditional] rows (batch 2a).  A variant's row is set to xts[tstart] when its segment starts.
+        Returns the edited latents [K, H, W, C] in the caller's order."""
+        if self.kind not in ("audioldm", "audioldm2", "tango"):
+            raise ValueError(f"edit_variants: engine kind {self.kind!r} is not supported (AudioLDM, AudioLDM2, TANGO)")
+        s = self.sched
+        T = s.num_inference_steps
+        if xts.shape[1] != 1:
+            raise ValueError(f"edit_variants edits ONE inverted clip; xts holds {xts.shape[1]}")
+        K = len(tstarts)
+        n_zs = T if zs is None else zs.shape[0]
+        order, segs = variant_plan(tstarts, n_zs, self.MAX_VARIANTS)
+        if len(cfg_tars) != K:
+            raise ValueError(f"{len(cfg_tars)} cfg_tar values for {K} variants")
+        tgt, neg = _variant_rows(cond_tgt, K, "cond_tgt"), _variant_rows(cond_neg, K, "cond_neg")
+        Z0 = segs[0]["tstart"]
+        eta_rows = self._etas_in_loop_order(eta, Z0)
+        has_noise = int(variant_noise(eta_rows) and zs is not None)
+        numel = self.C * self.H * self.W
+        v_pred = int(s.config.prediction_type == "v_prediction")
+        groups_all = [neg[v] for v in order] + [tgt[v] for v in order]
+        L0, L1 = self._ctx_lens(groups_all)
+        key = ("variants", K, T, tuple(sg["tstart"] for sg in segs), tuple(sg["a"] for sg in segs), L0, L1, v_pred,
+               has_noise, tuple(self._arith_for(2 * sg["a"]) for sg in segs))
+        plan = self._get_plan(key)
+        if plan is None:
+            plan = self._plans[key] = dict(
+                state=torch.zeros(4, dtype=torch.int32, device=self.device),
+                cur=torch.empty((K, self.H, self.W, self.C), device=self.device, dtype=torch.float32),
+                zs=torch.zeros((Z0, self.H, self.W, self.C), device=self.device, dtype=torch.float32),
+                coef=torch.zeros((Z0, L.COEF_STRIDE), device=self.device, dtype=torch.float32),
+                cfg=torch.zeros(K, device=self.device, dtype=torch.float32), segs=[])
+            for sg in segs:
+                a = sg["a"]
+                eng = self.unet(2 * a, L0, L1, share=1)
+                pre, post = Tape(self.device), Tape(self.device)
+                for blk in range(2):
+                    pre.copy2d(plan["cur"], eng.x_in[blk * a:(blk + 1) * a], rows=1, cols=a * numel, ld_src=a * numel,
+                               ld_dst=a * numel, name="x_in<-x_t")
+                post.step_variants(cur=plan["cur"], zs=plan["zs"] if has_noise else None, eps=eng.eps[:2 * a],
+                                   cfg=plan["cfg"], coef=plan["coef"], state=plan["state"], numel=numel, a=a, Z=Z0,
+                                   v_pred=v_pred)
+                post.advance(plan["state"])
+                pre.finalize()
+                post.finalize()
+                plan["segs"].append(dict(eng=eng, pre=pre, post=post))
+        cur = plan["cur"]
+        if has_noise:
+            plan["zs"].copy_(zs[:Z0, 0])
+        plan["coef"].copy_(self._coef_table(s, s.timesteps.cpu()[T - Z0:], eta_rows, "ddpm"))
+        plan["cfg"].copy_(torch.tensor([float(cfg_tars[v]) for v in order], dtype=torch.float32))
+        self._upload_timesteps(s.timesteps, T)
+        for sg, sp in zip(segs, plan["segs"]):
+            a = sg["a"]
+            self._set_cond(sp["eng"], groups_all[:a] + groups_all[K:K + a])
+            self._patch_time(sp["eng"], self.ts_dev, 1, 2 * a, offset=T - Z0, state=plan["state"])
+        plan["state"].zero_()
+        for sg, sp in zip(segs, plan["segs"]):
+            lo, hi = sg["join"]
+            cur[lo:hi].copy_(xts[sg["tstart"], 0].expand(hi - lo, -1, -1, -1))  # inversion_utils.py:203, per variant
+            eng, pre, post = sp["eng"], sp["pre"], sp["post"]
+
+            def body(eng=eng, pre=pre, post=post):
+                pre.run()
+                eng.tape.run()
+                post.run()
+            self._run_graph(body, sg["steps"], use_graph, sp)
+        return cur[variant_positions(order)]                       # advanced indexing: a copy, in the caller's order
 
     # ------------------------------------------------------------------ A16: DDIM baseline
     @torch.inference_mode()

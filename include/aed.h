@@ -91,6 +91,10 @@ enum aed_opcode {
     AED_OP_SA_STEP = 26,      /* CFG + StableAudWrapper.get_zs_from_xts / reverse_step_with_custom_noise (SDE-DPM-Solver++
                                  order 1 / 2, history on the device; models.py:1209-1271, :1282-1329)                      */
     AED_OP_GAUSS_SAMPLE = 27, /* mean + (softplus(scale) + 1e-4) * noise (Oobleck posterior sample, models.py:1132-1133)    */
+    AED_OP_REVERSE_STEP_VARIANTS = 28, /* one reverse step of `a` edit variants of ONE inverted clip at the same timestep: rows
+                                 [0, a) of x_t [K][numel], eps [a uncond | a cond], a per-variant scalar CFG (device float[a]),
+                                 ONE shared noise table; variant v is bit-identical to AED_OP_REVERSE_STEP with P = 1 and
+                                 cfg_scalar = cfg[v] (EditEngine.edit_variants)                                             */
     AED_OP_COUNT
 };
 
@@ -186,6 +190,15 @@ int aed_reverse_step_with_custom_noise(const float* xt, const float* eps_u, cons
                                        const float* cfg, float cfg_scalar, int n_prompts,
                                        const float* coef_host, int v_prediction, const float* z,
                                        float* prev_out, int64_t numel, void* stream);
+
+/* aed_reverse_step_with_custom_noise for n_variants edits of one inverted clip at the same timestep, one launch:
+ * xt [n_variants][numel], eps [n_variants uncond | n_variants cond][numel], cfg: DEVICE float[n_variants] (one scalar
+ * guidance per variant), z [numel] shared by every variant or NULL (no noise term), prev_out [n_variants][numel] (may be
+ * xt itself).  Row v is bit-identical to aed_reverse_step_with_custom_noise(xt[v], eps[v], eps[n_variants + v], NULL,
+ * cfg[v], 1, coef_host, v_prediction, z, prev_out[v], numel, stream).                                                   */
+int aed_reverse_step_variants(const float* xt, const float* eps, const float* cfg, int n_variants,
+                              const float* coef_host, int v_prediction, const float* z, float* prev_out,
+                              int64_t numel, void* stream);
 
 /* PipelineWrapper.sample_xts_from_x0 inner statement (models.py:81):
  * out = x0*sqrt_abar + noise*sqrt_1m_abar, for n_t rows (noise drawn by the host RNG).      */
