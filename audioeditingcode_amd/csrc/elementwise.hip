@@ -297,13 +297,71 @@ __global__ __launch_bounds__(256) void reverse_step_variants_kernel(VariantStepP
     }
 }
 
-static int launch_variants(const VariantStepParams& p, hipStream_t s, const char* what) {
+// ------------------------------------------------------------------------------------ K1 for edits of MANY inversions
+// The same step for `a` rows that belong to up to N different inverted clips (EditEngine.edit_clips): the noise tables are
+// one buffer zs [N][Z][numel] and the device vector src[a] names the table a row reads, so row v at loop step s uses
+// zs[src[v]][Z - s - 1].  Without src (the explicit form of aed_reverse_step_clips) zs holds one z row per row, [a][numel].
+// Everything else is reverse_step_variants_kernel: row v is bit-identical to it run on table src[v] with cfg[v] (same
+// cfg_combine form, shared reverse_update).  src is NOT range-checked here; the engine validates it on the host.
+// Plain grid-stride loop over element positions; the rows' loads (x_t, two eps, z) are independent of one another.
+struct ClipStepParams {
+    VariantStepParams v;   // zs: [N][Z][numel] with src, [a][numel] without; null -> no noise
+    const int* src;        // [a] table index of every row (device), or null
+};
+
+__global__ __launch_bounds__(256) void reverse_step_clips_kernel(ClipStepParams q) {
+    const VariantStepParams& p = q.v;
+    const int s = p.state ? p.state[0] * p.s_mul + p.s_off : p.s_imm;
+    float c0, c1, c2, c3, c4;
+    if (p.coef) { const float* c = p.coef + (size_t)s * AED_COEF_STRIDE; c0 = c[0]; c1 = c[1]; c2 = c[2]; c3 = c[3]; c4 = c[4]; }
+    else { c0 = p.c[0]; c1 = p.c[1]; c2 = p.c[2]; c3 = p.c[3]; c4 = p.c[4]; }
+    const float* eps_c = p.eps + (size_t)p.a * p.numel;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < p.numel; e += (size_t)gridDim.x * 256) {
+        for (int v0 = 0; v0 < p.a; v0 += 4) {                         // 4 rows' loads issued before the first store:
+            float x[4], u[4], c[4], zz[4];                            // out may alias cur, so stores would order them
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = v0 + j;
+                if (v >= p.a) break;
+                const size_t o = (size_t)v * p.numel + e;
+                x[j] = p.cur[o]; u[j] = p.eps[o]; c[j] = eps_c[o];
+                const size_t row = q.src ? (size_t)q.src[v] * p.Z + (size_t)(p.Z - s - 1) : (size_t)v;
+                zz[j] = p.zs ? p.zs[row * p.numel + e] : 0.f;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = v0 + j;
+                if (v >= p.a) break;
+                const float eps = u[j] + p.cfg[v] * (c[j] - u[j]);     // cfg_combine, P = 1
+                const size_t o = (size_t)v * p.numel + e;             // two calls: &zz[j] must not meet null in a select
+                if (p.zs) p.out[o] = reverse_update(x[j], eps, &zz[j], 0, p.v_pred, c0, c1, c2, c3, c4);
+                else p.out[o] = reverse_update(x[j], eps, nullptr, 0, p.v_pred, c0, c1, c2, c3, c4);
+            }
+        }
+    }
+}
+
+// what both step launchers refuse: null pointers, a < 1, an out that overlaps cur without being cur
+static int check_variants(const VariantStepParams& p, const char* what) {
     AED_REQUIRE(p.cur && p.out && p.eps && p.cfg, "%s: null pointer", what);
     AED_REQUIRE(p.a >= 1 && p.Z >= 0, "%s: bad variant count %d / Z %d", what, p.a, p.Z);
     AED_REQUIRE(p.out == p.cur || p.out + (size_t)p.a * p.numel <= p.cur || p.cur + (size_t)p.a * p.numel <= p.out,
                 "%s: out must be cur or not overlap it", what);
+    return 0;
+}
+
+static int launch_variants(const VariantStepParams& p, hipStream_t s, const char* what) {
+    if (int rc = check_variants(p, what)) return rc;
     if (p.numel == 0) return 0;
     hipLaunchKernelGGL(reverse_step_variants_kernel, dim3(grid_for(p.numel)), dim3(256), 0, s, p);
+    AED_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+static int launch_clips(const ClipStepParams& q, hipStream_t s, const char* what) {
+    if (int rc = check_variants(q.v, what)) return rc;
+    if (q.v.numel == 0) return 0;
+    hipLaunchKernelGGL(reverse_step_clips_kernel, dim3(grid_for(q.v.numel)), dim3(256), 0, s, q);
     AED_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -312,6 +370,8 @@ static int launch_variants(const VariantStepParams& p, hipStream_t s, const char
 //        p5=coef table (nullable)  p6=state (nullable)  p7=out (null => in place into p0)
 //   i0,i1=numel lo/hi  i2=a  i3=Z (#zs; 0 => p1 is the explicit z)  i4=s_imm  i5=v_pred  i6=has_noise
 //   i7=s_mul i8=s_off (step = state*s_mul + s_off)   f1..f5 = c0..c4 immediates (used when p5 is null)
+//   rows of several inversions: p3=src int[a] (device; null => the one shared table, as above)  i9=N, then p1 is
+//   zs [N][Z][numel] with Z >= 1 and row v reads table src[v]
 int launch_reverse_step_variants(const aed_op* op, hipStream_t s) {
     VariantStepParams p = {};
     p.cur = (const float*)op->p[0];
@@ -324,7 +384,11 @@ int launch_reverse_step_variants(const aed_op* op, hipStream_t s) {
     p.s_mul = op->i[7] > 0 ? op->i[7] : 1; p.s_off = op->i[8];
     for (int k = 0; k < 5; ++k) p.c[k] = op->f[1 + k];
     AED_REQUIRE(!op->i[6] || op->p[1], "reverse_step_variants: noise requested but zs is null");
-    return launch_variants(p, s, "reverse_step_variants");
+    const int* src = (const int*)op->p[3];
+    if (!src) return launch_variants(p, s, "reverse_step_variants");
+    AED_REQUIRE(op->i[9] >= 1, "reverse_step_variants: src given with %d noise tables", op->i[9]);
+    AED_REQUIRE(!p.zs || p.Z >= 1, "reverse_step_variants: src indexes tables zs [N][Z][numel], Z = %d", p.Z);
+    return launch_clips(ClipStepParams{p, src}, s, "reverse_step_variants");
 }
 
 // slots (both): p0=xts base | xt   p1=zs base | z   p2=eps_u  p3=eps_c  p4=cfg  p5=coef table  p6=state  p7=out
@@ -405,6 +469,18 @@ extern "C" int aed_reverse_step_variants(const float* xt, const float* eps, cons
     AED_REQUIRE(coef_host && numel >= 0, "aed_reverse_step_variants: null coefficients or negative numel");
     for (int k = 0; k < 5; ++k) p.c[k] = coef_host[k];
     return launch_variants(p, (hipStream_t)stream, "aed_reverse_step_variants");
+}
+
+extern "C" int aed_reverse_step_clips(const float* xt, const float* eps, const float* cfg, int n_rows,
+                                      const float* coef_host, int v_prediction, const float* z, float* prev_out,
+                                      int64_t numel, void* stream) {
+    VariantStepParams p = {};
+    p.s_mul = 1;
+    p.cur = xt; p.out = prev_out; p.zs = z; p.Z = 0; p.eps = eps; p.cfg = cfg; p.a = n_rows;
+    p.v_pred = v_prediction; p.numel = (size_t)numel;
+    AED_REQUIRE(coef_host && numel >= 0, "aed_reverse_step_clips: null coefficients or negative numel");
+    for (int k = 0; k < 5; ++k) p.c[k] = coef_host[k];
+    return launch_clips(ClipStepParams{p, nullptr}, (hipStream_t)stream, "aed_reverse_step_clips");
 }
 
 __global__ __launch_bounds__(256) void sample_xts_kernel(const float* __restrict__ x0, const float* __restrict__ noise,

@@ -142,6 +142,59 @@ def _variant_rows(cond, K, what):
     raise ValueError(f"edit_variants: {what} has {cond.rows} rows for {K} variants")
 
 
+def clip_plan(xts_list, zs_list, rows, T, latent_shape, max_rows=None):
+    """The host plan of EditEngine.edit_clips: checks the inverted clips and the rows (clip, tstart, ...) that edit them,
+    then returns (clips, tstarts, order, segments) with variant_plan's order and segments over the rows' tstarts.  Refuses
+    an empty list, more than `max_rows`, lists of different length, a clip that is not ONE inversion of `latent_shape`
+    (H, W, C) over T steps, a clip index outside the lists and a tstart outside [1, Z_c] of its OWN clip's noise maps."""
+    rows = list(rows)
+    if not rows:
+        raise ValueError("edit_clips: the list of rows is empty")
+    if max_rows is not None and len(rows) > max_rows:
+        raise ValueError(f"edit_clips: {len(rows)} rows in one call, at most {max_rows} "
+                         f"(batch.inversion_reverse_clips splits longer lists)")
+    N = len(xts_list)
+    if N < 1 or len(zs_list) != N:
+        raise ValueError(f"edit_clips: {N} trajectories and {len(zs_list)} noise tables (one of each per clip, at least one)")
+    want = (1, *latent_shape)
+    for c, (x, z) in enumerate(zip(xts_list, zs_list)):
+        if x.dim() != 5 or z.dim() != 5 or tuple(x.shape[1:]) != want or tuple(z.shape[1:]) != want:
+            raise ValueError(f"edit_clips: clip {c} has xts {tuple(x.shape)} / zs {tuple(z.shape)}; every clip must be ONE "
+                             f"inversion of latent shape [1, H, W, C] = {list(want)} (one latent shape per call)")
+        if x.shape[0] != T + 1:
+            raise ValueError(f"edit_clips: clip {c} holds {x.shape[0]} trajectory points, the schedule has T + 1 = {T + 1} "
+                             f"(one schedule per call)")
+    clips, tstarts = [], []
+    for k, row in enumerate(rows):
+        c, t = int(row[0]), int(row[1])
+        if not 0 <= c < N:
+            raise ValueError(f"edit_clips: row {k} names clip {c}, outside [0, {N}) (the clips the lists hold)")
+        if not 1 <= t <= zs_list[c].shape[0]:
+            raise ValueError(f"edit_clips: row {k} has tstart {t} outside [1, {zs_list[c].shape[0]}] (the number of noise "
+                             f"maps clip {c} holds)")
+        clips.append(c)
+        tstarts.append(t)
+    order, segs = variant_plan(tstarts, max(tstarts), max_rows)
+    return clips, tstarts, order, segs
+
+
+def clip_noise_fill(buf, zs_list):
+    """Fill the noise buffer [N, Z0, H, W, C] of an edit_clips plan: clip c's first min(Z0, Z_c) maps, zeros behind them
+    (never read: a row's tstart does not exceed its own clip's Z_c)."""
+    Z0 = buf.shape[1]
+    for c, z in enumerate(zs_list):
+        n = min(Z0, z.shape[0])
+        buf[c, :n].copy_(z[:n, 0])
+        buf[c, n:].zero_()
+    return buf
+
+
+def clip_join_rows(xts_list, clips, tstarts, order, seg):
+    """The rows that join the loop at segment `seg`: each from its OWN clip's xts[tstart] (inversion_utils.py:203)."""
+    lo, hi = seg["join"]
+    return torch.stack([xts_list[clips[order[i]]][tstarts[order[i]], 0] for i in range(lo, hi)])
+
+
 class LoopPlumbing:
     """What the device-resident loop engines share (this module's EditEngine, stable_audio.StableAudioEditEngine): an LRU
     of loop plans (persistent buffers + tapes + one instantiated hipGraph per loop shape) and the graph runner.
@@ -579,7 +632,75 @@ class EditEngine(LoopPlumbing):
         return cur.clone()
 
     # ------------------------------------------------------------------ K edits of one inversion
-    MAX_VARIANTS = 16       # variants per edit_variants call (U-Net batch <= 32); variants.inversion_reverse_variants chunks
+    MAX_VARIANTS = 16       # rows per edit_variants / edit_clips call (U-Net batch <= 32); variants.py and batch.py chunk
+
+    def _variant_loop(self, tag, order, segs, tgt, neg, cfgs, eta, noise_ok, fill_noise, join_rows, use_graph, src=None,
+                      n_tables=0):
+        """The segmented loop of edit_variants and edit_clips.  order / segs: variant_plan's; tgt / neg / cfgs: per row in
+        the caller's order; fill_noise(buf) loads the plan's noise buffer, join_rows(seg) returns the x_t rows that start
+        at a segment.  src (the table of every row, caller's order) with n_tables makes the noise buffer
+        [n_tables, Z0, H, W, C] and the step op read table src[row]; without it the one table [Z0, H, W, C] is shared.
+        Returns the rows [K, H, W, C] in the caller's order."""
+        s = self.sched
+        T = s.num_inference_steps
+        K = len(order)
+        Z0 = segs[0]["tstart"]
+        eta_rows = self._etas_in_loop_order(eta, Z0)
+        has_noise = int(variant_noise(eta_rows) and noise_ok)
+        numel = self.C * self.H * self.W
+        v_pred = int(s.config.prediction_type == "v_prediction")
+        groups_all = [neg[v] for v in order] + [tgt[v] for v in order]
+        L0, L1 = self._ctx_lens(groups_all)
+        tables = () if src is None else (n_tables,)
+        key = (tag, K, *tables, T, tuple(sg["tstart"] for sg in segs), tuple(sg["a"] for sg in segs), L0, L1, v_pred,
+               has_noise, tuple(self._arith_for(2 * sg["a"]) for sg in segs))
+        plan = self._get_plan(key)
+        if plan is None:
+            plan = self._plans[key] = dict(
+                state=torch.zeros(4, dtype=torch.int32, device=self.device),
+                cur=torch.empty((K, self.H, self.W, self.C), device=self.device, dtype=torch.float32),
+                zs=torch.zeros((*tables, Z0, self.H, self.W, self.C), device=self.device, dtype=torch.float32),
+                coef=torch.zeros((Z0, L.COEF_STRIDE), device=self.device, dtype=torch.float32),
+                cfg=torch.zeros(K, device=self.device, dtype=torch.float32),
+                src=None if src is None else torch.zeros(K, device=self.device, dtype=torch.int32), segs=[])
+            for sg in segs:
+                a = sg["a"]
+                eng = self.unet(2 * a, L0, L1, share=1)
+                pre, post = Tape(self.device), Tape(self.device)
+                for blk in range(2):
+                    pre.copy2d(plan["cur"], eng.x_in[blk * a:(blk + 1) * a], rows=1, cols=a * numel, ld_src=a * numel,
+                               ld_dst=a * numel, name="x_in<-x_t")
+                post.step_variants(cur=plan["cur"], zs=plan["zs"] if has_noise else None, eps=eng.eps[:2 * a],
+                                   cfg=plan["cfg"], coef=plan["coef"], state=plan["state"], numel=numel, a=a, Z=Z0,
+                                   v_pred=v_pred, src=plan["src"], N=n_tables)
+                post.advance(plan["state"])
+                pre.finalize()
+                post.finalize()
+                plan["segs"].append(dict(eng=eng, pre=pre, post=post))
+        cur = plan["cur"]
+        if has_noise:
+            fill_noise(plan["zs"])
+        plan["coef"].copy_(self._coef_table(s, s.timesteps.cpu()[T - Z0:], eta_rows, "ddpm"))
+        plan["cfg"].copy_(torch.tensor([float(cfgs[v]) for v in order], dtype=torch.float32))
+        if src is not None:
+            plan["src"].copy_(torch.tensor([src[v] for v in order], dtype=torch.int32))
+        self._upload_timesteps(s.timesteps, T)
+        for sg, sp in zip(segs, plan["segs"]):
+            a = sg["a"]
+            self._set_cond(sp["eng"], groups_all[:a] + groups_all[K:K + a])
+            self._patch_time(sp["eng"], self.ts_dev, 1, 2 * a, offset=T - Z0, state=plan["state"])
+        plan["state"].zero_()
+        for sg, sp in zip(segs, plan["segs"]):
+            lo, hi = sg["join"]
+            cur[lo:hi].copy_(join_rows(sg))                            # inversion_utils.py:203, per row
+            eng, pre, post = sp["eng"], sp["pre"], sp["post"]
+
+            def body(eng=eng, pre=pre, post=post):
+                pre.run()
+                eng.tape.run()
+                post.run()
+            self._run_graph(body, sg["steps"], use_graph, sp)
+        return cur[variant_positions(order)]                       # advanced indexing: a copy, in the caller's order
 
     @torch.inference_mode()
     def edit_variants(self, xts, zs, tstarts, cond_tgt, cond_neg, cfg_tars, eta=1.0, use_graph=True):
@@ -595,69 +716,45 @@ class EditEngine(LoopPlumbing):
         Returns the edited latents [K, H, W, C] in the caller's order."""
         if self.kind not in ("audioldm", "audioldm2", "tango"):
             raise ValueError(f"edit_variants: engine kind {self.kind!r} is not supported (AudioLDM, AudioLDM2, TANGO)")
-        s = self.sched
-        T = s.num_inference_steps
         if xts.shape[1] != 1:
             raise ValueError(f"edit_variants edits ONE inverted clip; xts holds {xts.shape[1]}")
         K = len(tstarts)
-        n_zs = T if zs is None else zs.shape[0]
+        n_zs = self.sched.num_inference_steps if zs is None else zs.shape[0]
         order, segs = variant_plan(tstarts, n_zs, self.MAX_VARIANTS)
         if len(cfg_tars) != K:
             raise ValueError(f"{len(cfg_tars)} cfg_tar values for {K} variants")
         tgt, neg = _variant_rows(cond_tgt, K, "cond_tgt"), _variant_rows(cond_neg, K, "cond_neg")
-        Z0 = segs[0]["tstart"]
-        eta_rows = self._etas_in_loop_order(eta, Z0)
-        has_noise = int(variant_noise(eta_rows) and zs is not None)
-        numel = self.C * self.H * self.W
-        v_pred = int(s.config.prediction_type == "v_prediction")
-        groups_all = [neg[v] for v in order] + [tgt[v] for v in order]
-        L0, L1 = self._ctx_lens(groups_all)
-        key = ("variants", K, T, tuple(sg["tstart"] for sg in segs), tuple(sg["a"] for sg in segs), L0, L1, v_pred,
-               has_noise, tuple(self._arith_for(2 * sg["a"]) for sg in segs))
-        plan = self._get_plan(key)
-        if plan is None:
-            plan = self._plans[key] = dict(
-                state=torch.zeros(4, dtype=torch.int32, device=self.device),
-                cur=torch.empty((K, self.H, self.W, self.C), device=self.device, dtype=torch.float32),
-                zs=torch.zeros((Z0, self.H, self.W, self.C), device=self.device, dtype=torch.float32),
-                coef=torch.zeros((Z0, L.COEF_STRIDE), device=self.device, dtype=torch.float32),
-                cfg=torch.zeros(K, device=self.device, dtype=torch.float32), segs=[])
-            for sg in segs:
-                a = sg["a"]
-                eng = self.unet(2 * a, L0, L1, share=1)
-                pre, post = Tape(self.device), Tape(self.device)
-                for blk in range(2):
-                    pre.copy2d(plan["cur"], eng.x_in[blk * a:(blk + 1) * a], rows=1, cols=a * numel, ld_src=a * numel,
-                               ld_dst=a * numel, name="x_in<-x_t")
-                post.step_variants(cur=plan["cur"], zs=plan["zs"] if has_noise else None, eps=eng.eps[:2 * a],
-                                   cfg=plan["cfg"], coef=plan["coef"], state=plan["state"], numel=numel, a=a, Z=Z0,
-                                   v_pred=v_pred)
-                post.advance(plan["state"])
-                pre.finalize()
-                post.finalize()
-                plan["segs"].append(dict(eng=eng, pre=pre, post=post))
-        cur = plan["cur"]
-        if has_noise:
-            plan["zs"].copy_(zs[:Z0, 0])
-        plan["coef"].copy_(self._coef_table(s, s.timesteps.cpu()[T - Z0:], eta_rows, "ddpm"))
-        plan["cfg"].copy_(torch.tensor([float(cfg_tars[v]) for v in order], dtype=torch.float32))
-        self._upload_timesteps(s.timesteps, T)
-        for sg, sp in zip(segs, plan["segs"]):
-            a = sg["a"]
-            self._set_cond(sp["eng"], groups_all[:a] + groups_all[K:K + a])
-            self._patch_time(sp["eng"], self.ts_dev, 1, 2 * a, offset=T - Z0, state=plan["state"])
-        plan["state"].zero_()
-        for sg, sp in zip(segs, plan["segs"]):
-            lo, hi = sg["join"]
-            cur[lo:hi].copy_(xts[sg["tstart"], 0].expand(hi - lo, -1, -1, -1))  # inversion_utils.py:203, per variant
-            eng, pre, post = sp["eng"], sp["pre"], sp["post"]
+        return self._variant_loop(
+            "variants", order, segs, tgt, neg, cfg_tars, eta, zs is not None,
+            fill_noise=lambda buf: buf.copy_(zs[:buf.shape[0], 0]),
+            join_rows=lambda sg: xts[sg["tstart"], 0].expand(sg["join"][1] - sg["join"][0], -1, -1, -1),
+            use_graph=use_graph)
 
-            def body(eng=eng, pre=pre, post=post):
-                pre.run()
-                eng.tape.run()
-                post.run()
-            self._run_graph(body, sg["steps"], use_graph, sp)
-        return cur[variant_positions(order)]                       # advanced indexing: a copy, in the caller's order
+    # ------------------------------------------------------------------ edits of many inversions
+    @torch.inference_mode()
+    def edit_clips(self, xts_list, zs_list, rows, eta=1.0, use_graph=True):
+        """K edits of up to N DIFFERENT inverted clips in one device-resident loop.  xts_list[c] [T+1, 1, H, W, C] and
+        zs_list[c] [Z_c, 1, H, W, C] are clip c's trajectory and noise maps (channels-last, as invert() returns them; one
+        latent shape and one schedule per call).  rows: a list of (clip, tstart, cond_tgt, cond_neg, cfg_tar) with one-row
+        Conditioning objects; row k is `edit(xts_list[clip], zs_list[clip], tstart, cond_tgt, cond_neg, [cfg_tar], eta)`.
+        eta: one float, or the reference's per-step list (indexed by noise-map number) shared by every row.
+
+        The loop is edit_variants' (rows sorted by tstart, largest first; segments between the distinct tstarts at U-Net
+        batch 2a; the same engines, tapes and graphs per segment), except that a row joins from its own clip's
+        xts[tstart] and the step reads its own clip's noise table (zs [N, Z0, H, W, C], Z0 = max tstart; src[row] = clip).
+        Returns the edited latents [K, H, W, C] in the caller's order."""
+        if self.kind not in ("audioldm", "audioldm2", "tango"):
+            raise ValueError(f"edit_clips: engine kind {self.kind!r} is not supported (AudioLDM, AudioLDM2, TANGO)")
+        clips, tstarts, order, segs = clip_plan(xts_list, zs_list, rows, self.sched.num_inference_steps,
+                                                (self.H, self.W, self.C), self.MAX_VARIANTS)
+        K = len(clips)
+        tgt = _variant_rows([r[2] for r in rows], K, "cond_tgt")
+        neg = _variant_rows([r[3] for r in rows], K, "cond_neg")
+        return self._variant_loop(
+            "clips", order, segs, tgt, neg, [r[4] for r in rows], eta, True,
+            fill_noise=lambda buf: clip_noise_fill(buf, zs_list),
+            join_rows=lambda sg: clip_join_rows(xts_list, clips, tstarts, order, sg),
+            use_graph=use_graph, src=clips, n_tables=len(xts_list))     # clips: validated in clip_plan, all < N
 
     # ------------------------------------------------------------------ A16: DDIM baseline
     @torch.inference_mode()

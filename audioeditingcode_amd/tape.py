@@ -503,15 +503,16 @@ class Tape:
                   [xts, zs, eps_u, eps_c, cfg, coef, state, out], name=name, nbytes=4 * numel * 6)
 
     def step_variants(self, *, cur, zs, eps, cfg, coef, state, numel, a, Z, v_pred=0, out=None, s_imm=0,
-                      c_imm=(0, 0, 0, 0, 0), s_mul=1, s_off=0, name="step_variants"):
+                      c_imm=(0, 0, 0, 0, 0), s_mul=1, s_off=0, src=None, N=0, name="step_variants"):
         """One reverse step of the `a` edit variants in rows [0, a) of cur [K, numel] (AED_OP_REVERSE_STEP_VARIANTS):
         eps [a uncond | a cond], cfg a device float[>= a], zs the shared noise table [Z, numel] (None: no noise term;
-        Z = 0: zs is one explicit z).  out=None steps cur in place."""
+        Z = 0: zs is one explicit z).  out=None steps cur in place.  src (a device int32[>= a]) makes the rows edits of up
+        to N inversions: zs is then [N, Z, numel] and row v reads table src[v] (EditEngine.edit_clips)."""
         has_noise = int(zs is not None)
         self._add(L.OP_REVERSE_STEP_VARIANTS, [numel & 0xFFFFFFFF, numel >> 32, a, Z if has_noise else 0, s_imm, v_pred,
-                                               has_noise, s_mul, s_off],
-                  [0.0, *c_imm], [cur, zs, eps, None, cfg, coef, state, out], name=name,
-                  nbytes=4 * numel * (4 * a + has_noise))
+                                               has_noise, s_mul, s_off, N if src is not None else 0],
+                  [0.0, *c_imm], [cur, zs, eps, src, cfg, coef, state, out], name=name,
+                  nbytes=4 * numel * (4 * a + has_noise * (1 if src is None else a)))
 
     # ------------------------------------------------------------------ Stable Audio Open ops (csrc/stable_audio.hip)
     def rotary(self, x, cos, sin, *, M, N, H, D, R, ld=None, nsec=2, sec_stride=None, name="rotary"):

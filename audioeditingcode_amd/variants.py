@@ -39,7 +39,8 @@ def expand_grid(target_prompts, cfg_tars, tstarts, target_neg_prompts=("",)):
             for (p, n), c, t in itertools.product(zip(target_prompts, negs), cfg_tars, tstarts)]
 
 
-def _slug(text, n=32):
+def slug(text, n=32):
+    """A prompt as a piece of a file name: runs of other characters become one underscore, at most n characters."""
     s = re.sub(r"[^A-Za-z0-9]+", "_", text).strip("_")[:n].rstrip("_")
     return s or "empty"
 
@@ -47,11 +48,11 @@ def _slug(text, n=32):
 def manifest(variants):
     """One record per variant, in order: index, prompts, cfg_tar, tstart and the file name its audio is written to."""
     return [dict(index=i, target_prompt=v.target_prompt, target_neg_prompt=v.target_neg_prompt, cfg_tar=v.cfg_tar,
-                 tstart=v.tstart, file=f"{i:03d}_{_slug(v.target_prompt)}_cfg{v.cfg_tar:g}_t{v.tstart}.wav")
+                 tstart=v.tstart, file=f"{i:03d}_{slug(v.target_prompt)}_cfg{v.cfg_tar:g}_t{v.tstart}.wav")
             for i, v in enumerate(variants)]
 
 
-def _eta_for_engine(etas, n_zs):
+def eta_for_engine(etas, n_zs):
     """The reference's eta argument (a number, or a per-step list indexed by noise-map number) in the form the loop
     engine takes: a float when it is constant over the noise maps used, else that list."""
     if etas is None:
@@ -87,7 +88,7 @@ def inversion_reverse_variants(model, xts, zs, variants, etas=1.0, chunk=None):
         return box[p]
     xts_c = ed.to_nhwc(xts.unsqueeze(1))
     zs_c = ed.to_nhwc(zs.unsqueeze(1))
-    eta = _eta_for_engine(etas, zs.shape[0])
+    eta = eta_for_engine(etas, zs.shape[0])
     order = sorted(range(len(variants)), key=lambda v: -variants[v].tstart)
     out = [None] * len(variants)
     for lo in range(0, len(order), chunk):

@@ -94,7 +94,9 @@ enum aed_opcode {
     AED_OP_REVERSE_STEP_VARIANTS = 28, /* one reverse step of `a` edit variants of ONE inverted clip at the same timestep: rows
                                  [0, a) of x_t [K][numel], eps [a uncond | a cond], a per-variant scalar CFG (device float[a]),
                                  ONE shared noise table; variant v is bit-identical to AED_OP_REVERSE_STEP with P = 1 and
-                                 cfg_scalar = cfg[v] (EditEngine.edit_variants)                                             */
+                                 cfg_scalar = cfg[v] (EditEngine.edit_variants).  With a device int[a] `src` (slot p3) and N
+                                 tables zs [N][Z][numel] the rows belong to up to N inversions and row v reads table src[v]
+                                 (EditEngine.edit_clips); without src the op is unchanged                                  */
     AED_OP_COUNT
 };
 
@@ -199,6 +201,12 @@ int aed_reverse_step_with_custom_noise(const float* xt, const float* eps_u, cons
 int aed_reverse_step_variants(const float* xt, const float* eps, const float* cfg, int n_variants,
                               const float* coef_host, int v_prediction, const float* z, float* prev_out,
                               int64_t numel, void* stream);
+
+/* aed_reverse_step_variants for n_rows edits that belong to different inverted clips: the same arguments, but z holds one
+ * noise map per row, [n_rows][numel] (or NULL: no noise term).  Row v is bit-identical to aed_reverse_step_variants on
+ * (xt[v], {eps[v], eps[n_rows + v]}, cfg[v], 1 variant, z[v]).                                                          */
+int aed_reverse_step_clips(const float* xt, const float* eps, const float* cfg, int n_rows, const float* coef_host,
+                           int v_prediction, const float* z, float* prev_out, int64_t numel, void* stream);
 
 /* PipelineWrapper.sample_xts_from_x0 inner statement (models.py:81):
  * out = x0*sqrt_abar + noise*sqrt_1m_abar, for n_t rows (noise drawn by the host RNG).      */
