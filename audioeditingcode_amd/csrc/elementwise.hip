@@ -233,14 +233,20 @@ __global__ __launch_bounds__(256) void invert_step_kernel(StepParams p) {
 
 // x_{t-1} of reverse_step_with_custom_noise (models.py:119-158) in the reference's fp32 expression order; shared by the
 // one-edit and the K-variant step kernels so that both compute the same bits from the same inputs.
-__device__ __forceinline__ float reverse_update(float x, float eps, const float* z, size_t e, int v_pred, float c0,
-                                                float c1, float c2, float c3, float c4) {
-    float x0, dir;
+__device__ __forceinline__ float reverse_update_x0(float x, float eps, const float* z, size_t e, int v_pred, float c0,
+                                                   float c1, float c2, float c3, float c4, float& x0) {
+    float dir;
     if (!v_pred) { x0 = (x - c0 * eps) / c1; dir = eps; }
     else { x0 = c1 * x - c0 * eps; dir = c1 * eps + c0 * x; }
     float prev = c2 * x0 + c3 * dir;
     if (z) prev = prev + c4 * z[e];
     return prev;
+}
+// the step kernels that do not need x0_hat (everything but the PC drift step)
+__device__ __forceinline__ float reverse_update(float x, float eps, const float* z, size_t e, int v_pred, float c0,
+                                                float c1, float c2, float c3, float c4) {
+    float x0;
+    return reverse_update_x0(x, eps, z, e, v_pred, c0, c1, c2, c3, c4, x0);
 }
 
 __global__ __launch_bounds__(256) void reverse_step_kernel(StepParams p) {
@@ -391,6 +397,139 @@ int launch_reverse_step_variants(const aed_op* op, hipStream_t s) {
     return launch_clips(ClipStepParams{p, src}, s, "reverse_step_variants");
 }
 
+// ------------------------------------------------------------------------------------ K1 for K principal-component drifts
+// One step of `a` rows that replay ONE recorded trajectory (EditEngine.drift_variants): reverse_step_variants_kernel's
+// CFG combine and step with the recorded noise, then -- for a row that has a non-zero weight at this loop step --
+// apply_drift (pc_drift.py:201-278) in the reference's expression order and the optional fix_alpha blend towards the
+// undrifted parallel trajectory (main_pc_apply_drift.py:185-187), all in place on cur.  The PC directions of loop step s
+// are slab s - s_first of vecs [S][n_ev][numel]; the weights w [S][a_max][n_ev] hold amount * sqrt(lambda_e) where PC e
+// is in the row's set and s in its window, 0 elsewhere (host-filled; the kernel sees neither amounts nor windows).  A row
+// whose weights are all zero at this step (uniform across the wave: a branch, not a multiply by zero; this includes a row
+// inside its window with amount 0 or a zero eigenvalue, which is then not blended either) takes exactly
+// reverse_step_variants_kernel's arithmetic, so the trunk row and every row outside its window are bit-identical to it.
+// The parallel x_{t-1} is row s + par_off of the table `par` (the stored trajectory), the explicit `par` [numel]
+// (fix_mode 1 without a step table), or the stepped row 0 of this launch (fix_mode 2: the trunk row, weights zero).
+// Grid-stride loop over element positions; a thread walks the rows in groups of 4 whose loads are all issued before the
+// group's first store (out is cur), and keeps the element's directions, noise, mask and parallel value in registers.
+#define AED_DRIFT_MAX_EV 8
+struct DriftStepParams {
+    VariantStepParams v;   // out == cur; zs: [Z][numel] device-indexed, one explicit z (Z == 0) or null
+    const float* vecs;     // [S][n_ev][numel]
+    const float* w;        // [S][a_max][n_ev]
+    const float* mask;     // [numel] or null
+    const float* par;      // fix_mode 1: table [*][numel] (par_table) or one explicit row [numel]
+    int n_ev, a_max, s_first, S, shift_np, fix_mode, par_table, par_off;
+    float fix_alpha;
+};
+
+__global__ __launch_bounds__(256) void drift_step_variants_kernel(DriftStepParams q) {
+    const VariantStepParams& p = q.v;
+    const int s = p.state ? p.state[0] * p.s_mul + p.s_off : p.s_imm;
+    float c0, c1, c2, c3, c4;
+    if (p.coef) { const float* c = p.coef + (size_t)s * AED_COEF_STRIDE; c0 = c[0]; c1 = c[1]; c2 = c[2]; c3 = c[3]; c4 = c[4]; }
+    else { c0 = p.c[0]; c1 = p.c[1]; c2 = p.c[2]; c3 = p.c[3]; c4 = p.c[4]; }
+    const float* z = nullptr;
+    if (p.zs) z = (p.Z > 0) ? p.zs + (size_t)(p.Z - s - 1) * p.numel : p.zs;
+    const float* eps_c = p.eps + (size_t)p.a * p.numel;
+    const int slab = s - q.s_first;
+    const bool in_win = slab >= 0 && slab < q.S;              // outside the union of the windows no row drifts
+    const float* vecs = in_win ? q.vecs + (size_t)slab * q.n_ev * p.numel : nullptr;
+    const float* w = in_win ? q.w + (size_t)slab * q.a_max * q.n_ev : nullptr;
+    const float* par = nullptr;
+    if (q.fix_mode == 1) par = q.par_table ? q.par + (size_t)(s + q.par_off) * p.numel : q.par;
+    const float k_np = c1 / c0;                               // sqrt(abar_t) / sqrt(1 - abar_t)
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < p.numel; e += (size_t)gridDim.x * 256) {
+        float vv[AED_DRIFT_MAX_EV];
+#pragma unroll
+        for (int k = 0; k < AED_DRIFT_MAX_EV; ++k) vv[k] = (in_win && k < q.n_ev) ? vecs[(size_t)k * p.numel + e] : 0.f;
+        const float zz = z ? z[e] : 0.f;
+        const float mk = q.fix_mode ? q.mask[e] : 1.f;
+        float pv = par ? par[e] : 0.f;                         // fix_mode 2: set by row 0 below
+        for (int v0 = 0; v0 < p.a; v0 += 4) {
+            float x[4], u[4], c[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = v0 + j;
+                if (v >= p.a) break;
+                const size_t o = (size_t)v * p.numel + e;
+                x[j] = p.cur[o]; u[j] = p.eps[o]; c[j] = eps_c[o];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = v0 + j;
+                if (v >= p.a) break;
+                const float eps = u[j] + p.cfg[v] * (c[j] - u[j]);     // cfg_combine, P = 1
+                float x0, prev;                                       // two calls: &zz must not meet null in a select
+                if (z) prev = reverse_update_x0(x[j], eps, &zz, 0, p.v_pred, c0, c1, c2, c3, c4, x0);
+                else prev = reverse_update_x0(x[j], eps, nullptr, 0, p.v_pred, c0, c1, c2, c3, c4, x0);
+                bool drifts = false;
+                if (in_win)
+                    for (int k = 0; k < q.n_ev; ++k) drifts = drifts || w[v * q.n_ev + k] != 0.f;
+                if (drifts) {                                         // apply_drift, pc_drift.py:236-278
+                    float shift = 0.f;
+#pragma unroll
+                    for (int k = 0; k < AED_DRIFT_MAX_EV; ++k) {
+                        if (k >= q.n_ev) break;
+                        const float term = w[v * q.n_ev + k] * vv[k];
+                        shift = (k == 0) ? term : shift + term;
+                    }
+                    const float mean = z ? prev - c4 * zz : prev;
+                    float eps_hat = (mean - c2 * x0) / c3;
+                    if (q.shift_np) eps_hat = eps_hat - k_np * shift;
+                    prev = c2 * (x0 + shift) + c3 * eps_hat;
+                    if (z) prev = prev + c4 * zz;
+                    if (q.fix_mode) prev = mk * prev + (1.f - mk) * (q.fix_alpha * pv + (1.f - q.fix_alpha) * prev);
+                }
+                if (v == 0 && q.fix_mode == 2) pv = prev;             // the trunk row: the undrifted x_{t-1}
+                p.out[(size_t)v * p.numel + e] = prev;
+            }
+        }
+    }
+}
+
+static int launch_drift(const DriftStepParams& q, hipStream_t s, const char* what) {
+    if (int rc = check_variants(q.v, what)) return rc;
+    AED_REQUIRE(q.v.out == q.v.cur, "%s: the op steps cur in place", what);
+    AED_REQUIRE(q.vecs && q.w, "%s: null direction / weight table", what);
+    AED_REQUIRE(q.n_ev >= 1 && q.n_ev <= AED_DRIFT_MAX_EV, "%s: n_ev %d outside [1, %d]", what, q.n_ev, AED_DRIFT_MAX_EV);
+    AED_REQUIRE(q.a_max >= q.v.a && q.S >= 1, "%s: weight rows %d for %d rows / %d direction slabs", what, q.a_max, q.v.a, q.S);
+    AED_REQUIRE(q.fix_mode >= 0 && q.fix_mode <= 2, "%s: fix mode %d", what, q.fix_mode);
+    AED_REQUIRE(!q.fix_mode || q.mask, "%s: fix_alpha needs a mask", what);
+    AED_REQUIRE(q.fix_mode != 1 || q.par, "%s: fix_alpha needs a parallel source (a table, or row 0)", what);
+    if (q.v.numel == 0) return 0;
+    hipLaunchKernelGGL(drift_step_variants_kernel, dim3(grid_for(q.v.numel)), dim3(256), 0, s, q);
+    AED_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// slots: p0=cur [K][numel] (rows [0, a) stepped IN PLACE)  p1=zs base | z | null (no noise)  p2=eps [2a][numel]
+//        p3=vecs [S][n_ev][numel]  p4=cfg [a] (device)  p5=coef table (nullable)  p6=state (nullable)
+//        p7=w [S][a_max][n_ev]  p8=mask [numel] (nullable)  p9=parallel trajectory table [*][numel] (nullable)
+//   i0,i1=numel lo/hi  i2=a  i3=Z (#zs; 0 => p1 is the explicit z)  i4=s_imm  i5=v_pred  i6=has_noise
+//   i7=s_mul i8=s_off (step = state*s_mul + s_off)  i9=n_ev (1..8)  i10=a_max  i11=s_first  i12=S (loop steps
+//   [s_first, s_first + S) read slab step - s_first; outside them no row drifts)  i13=shift_x0_for_np
+//   i14=fix mode: 0 no fix_alpha blend, 1 parallel x_{t-1} = row step + i15 of p9, 2 = the stepped row 0 (weights zero)
+//   i15=par_off   f0=fix_alpha  f1..f5 = c0..c4 immediates (used when p5 is null)
+int launch_drift_step_variants(const aed_op* op, hipStream_t s) {
+    DriftStepParams q = {};
+    VariantStepParams& p = q.v;
+    p.cur = (const float*)op->p[0]; p.out = (float*)op->p[0];
+    p.zs = op->i[6] ? (const float*)op->p[1] : nullptr;
+    p.eps = (const float*)op->p[2]; p.cfg = (const float*)op->p[4];
+    p.coef = (const float*)op->p[5]; p.state = (const int*)op->p[6];
+    p.numel = (size_t)(uint32_t)op->i[0] | ((size_t)(uint32_t)op->i[1] << 32);
+    p.a = op->i[2]; p.Z = op->i[3]; p.s_imm = op->i[4]; p.v_pred = op->i[5];
+    p.s_mul = op->i[7] > 0 ? op->i[7] : 1; p.s_off = op->i[8];
+    for (int k = 0; k < 5; ++k) p.c[k] = op->f[1 + k];
+    AED_REQUIRE(!op->i[6] || op->p[1], "drift_step_variants: noise requested but zs is null");
+    q.vecs = (const float*)op->p[3]; q.w = (const float*)op->p[7];
+    q.mask = (const float*)op->p[8]; q.par = (const float*)op->p[9];
+    q.n_ev = op->i[9]; q.a_max = op->i[10]; q.s_first = op->i[11]; q.S = op->i[12]; q.shift_np = op->i[13];
+    q.fix_mode = op->i[14]; q.par_table = 1; q.par_off = op->i[15];
+    q.fix_alpha = op->f[0];
+    return launch_drift(q, s, "drift_step_variants");
+}
+
 // slots (both): p0=xts base | xt   p1=zs base | z   p2=eps_u  p3=eps_c  p4=cfg  p5=coef table  p6=state  p7=out
 //   i0,i1=numel lo/hi  i2=P  i3=T (invert: #steps; reverse: #zs, 0 => p1 is the explicit z)  i4=s_imm
 //   i5=v_pred  i6=numerical_fix | has_noise   i7=s_mul i8=s_off (step = state*s_mul + s_off; timestep-batched loops)
@@ -481,6 +620,23 @@ extern "C" int aed_reverse_step_clips(const float* xt, const float* eps, const f
     AED_REQUIRE(coef_host && numel >= 0, "aed_reverse_step_clips: null coefficients or negative numel");
     for (int k = 0; k < 5; ++k) p.c[k] = coef_host[k];
     return launch_clips(ClipStepParams{p, nullptr}, (hipStream_t)stream, "aed_reverse_step_clips");
+}
+
+extern "C" int aed_drift_step_variants(float* xt, const float* eps, const float* cfg, int n_rows, const float* coef_host,
+                                       int v_prediction, const float* z, const float* vecs, const float* w, int n_ev,
+                                       int shift_x0_for_np, const float* mask, const float* parallel, int fix_mode,
+                                       float fix_alpha, int64_t numel, void* stream) {
+    DriftStepParams q = {};
+    VariantStepParams& p = q.v;
+    p.s_mul = 1;
+    p.cur = xt; p.out = xt; p.zs = z; p.Z = 0; p.eps = eps; p.cfg = cfg; p.a = n_rows;
+    p.v_pred = v_prediction; p.numel = (size_t)numel;
+    AED_REQUIRE(coef_host && numel >= 0, "aed_drift_step_variants: null coefficients or negative numel");
+    for (int k = 0; k < 5; ++k) p.c[k] = coef_host[k];
+    q.vecs = vecs; q.w = w; q.mask = mask; q.par = parallel;
+    q.n_ev = n_ev; q.a_max = n_rows; q.s_first = 0; q.S = 1; q.shift_np = shift_x0_for_np;
+    q.fix_mode = fix_mode; q.par_table = 0; q.par_off = 0; q.fix_alpha = fix_alpha;
+    return launch_drift(q, (hipStream_t)stream, "aed_drift_step_variants");
 }
 
 __global__ __launch_bounds__(256) void sample_xts_kernel(const float* __restrict__ x0, const float* __restrict__ noise,

@@ -195,6 +195,113 @@ def clip_join_rows(xts_list, clips, tstarts, order, seg):
     return torch.stack([xts_list[clips[order[i]]][tstarts[order[i]], 0] for i in range(lo, hi)])
 
 
+MAX_DRIFT_EV = 8         # PCs per timestep the drift step kernel takes (AED_DRIFT_MAX_EV in csrc/elementwise.hip)
+
+
+def _window(v):
+    """(drift_start, drift_end) of a drift variant: an object with these attributes, or the pair itself."""
+    if hasattr(v, "drift_start"):
+        return int(v.drift_start), int(v.drift_end)
+    return int(v[0]), int(v[1])
+
+
+def drift_plan(variants, T, max_variants=None):
+    """The segment plan of EditEngine.drift_variants.  A variant drifts on the loop steps [T - drift_start, T - drift_end)
+    of the T-step replay (main_pc_apply_drift.py:141-143).  Row 0 of the loop is the undrifted trunk; `order` lists the
+    variants sorted by drift_start, largest first (stable), and sorted variant i is row 1 + i.  A row joins the loop at
+    the first step of its own window as a copy of the trunk row, so the rows active in a segment are a prefix:
+    segment j is dict(start: first loop step, steps, tstart: T - start (steps left; variant_plan's field), a: active rows
+    with the trunk, join=(lo, hi): the rows that start at this segment).  The first segment starts at step 0 with the
+    trunk (and every variant whose drift_start is T).  Refuses an empty list, more than `max_variants`,
+    drift_start <= drift_end and a window outside [0, T]."""
+    wins = [_window(v) for v in variants]
+    if not wins:
+        raise ValueError("drift_variants: the list of variants is empty")
+    if max_variants is not None and len(wins) > max_variants:
+        raise ValueError(f"drift_variants: {len(wins)} variants in one call, at most {max_variants} "
+                         f"(drift_grid.apply_pcs_grid splits longer lists)")
+    for k, (ds, de) in enumerate(wins):
+        if ds <= de:
+            raise ValueError(f"drift_variants: variant {k} has drift_start {ds} <= drift_end {de} (the window runs from "
+                             f"drift_start down to drift_end)")
+        if not (0 <= de and ds <= T):
+            raise ValueError(f"drift_variants: variant {k} has the window {ds} -> {de} outside [0, {T}] (the diffusion "
+                             f"steps of the recorded trajectory)")
+    order = sorted(range(len(wins)), key=lambda v: -wins[v][0])
+    starts = sorted({0} | {T - ds for ds, _ in wins})
+    segs, a = [], 1
+    for j, st in enumerate(starts):
+        n = sum(1 for ds, _ in wins if T - ds == st)
+        lo = 0 if j == 0 else a
+        a += n
+        end = starts[j + 1] if j + 1 < len(starts) else T
+        segs.append(dict(start=st, steps=end - st, tstart=T - st, a=a, join=(lo, a)))
+    return order, segs
+
+
+def drift_union(variants, T):
+    """(s_first, S): the loop steps [s_first, s_first + S) between the first window's opening and the last one's close."""
+    wins = [_window(v) for v in variants]
+    s_first = T - max(ds for ds, _ in wins)
+    return s_first, T - min(de for _, de in wins) - s_first
+
+
+def random_directions(eigdata):
+    """A copy of eigdata in which every timestep's directions are random ones of the same norm
+    (main_pc_apply_drift.py:96-100); the other fields are shared, the argument is left as it is."""
+    out = {}
+    for t, e in eigdata.items():
+        r = torch.randn_like(e["eigvec"], dtype=torch.float32)
+        out[t] = {**e, "eigvec": r / r.norm() * e["eigvec"].norm()}
+    return out
+
+
+def drift_tables(eigdata, timesteps, T, variants, use_specific_ts_pc=None, evals=None, rand_v=False):
+    """The direction and weight tables of EditEngine.drift_variants from a `.pt` file's eigdata
+    ({timestep: dict(eigvec [n_ev, C, H, W], eigval [n_ev])}), with pc_drift._stored_pc's table choices:
+    `use_specific_ts_pc` takes every step's vectors from timesteps[T - use_specific_ts_pc], `evals` ({timestep: numpy
+    [n_ev]}) replaces the stored eigenvalues, `rand_v` replaces every stored direction by a random one of the same norm
+    (random_directions, drawn here; a caller that builds several tables of one sweep draws once itself).  variants:
+    objects with evs (PC numbers from 1), amount, drift_start, drift_end.  Returns (vecs [S, n_ev, C, H, W],
+    w [S, K, n_ev]) on the CPU for the loop steps
+    drift_union(variants, T): w[s, v, e] = amount_v * sqrt(lambda_e(t_s)) where PC e + 1 is in variant v's set and s in
+    its window, else 0; a step inside the union that no window covers has zero weights and zero vectors."""
+    variants = list(variants)
+    drift_plan(variants, T)
+    some = next(iter(eigdata.values()))["eigvec"]
+    n_ev, shape = some.shape[0], tuple(some.shape[1:])
+    if not 1 <= n_ev <= MAX_DRIFT_EV:
+        raise ValueError(f"drift_variants: the file holds {n_ev} PCs per timestep, the drift step takes 1 to {MAX_DRIFT_EV}")
+    for k, v in enumerate(variants):
+        evs = [int(e) for e in v.evs]
+        if not evs or any(not 1 <= e <= n_ev for e in evs):
+            raise ValueError(f"drift_variants: variant {k} names the PCs {evs}, outside [1, {n_ev}] (the PCs the file holds)")
+    s_first, S = drift_union(variants, T)
+    vecs = torch.zeros(S, n_ev, *shape, dtype=torch.float32)
+    w = torch.zeros(S, len(variants), n_ev, dtype=torch.float32)
+    ts = [int(t) for t in timesteps]
+    if rand_v:
+        eigdata = random_directions(eigdata)
+    for j in range(S):
+        it = s_first + j
+        rows = [k for k, v in enumerate(variants) if T - _window(v)[0] <= it < T - _window(v)[1]]
+        if not rows:
+            continue
+        t = ts[it]
+        vec_t = t if use_specific_ts_pc is None else ts[T - int(use_specific_ts_pc)]
+        if vec_t not in eigdata or (evals is None and t not in eigdata) or (evals is not None and t not in evals):
+            raise ValueError(f"drift_variants: no principal components for timestep {t} (loop step {it}); the file covers "
+                             f"the timesteps {sorted(eigdata)[0]}..{sorted(eigdata)[-1]}")
+        vec = eigdata[vec_t]["eigvec"].detach().to("cpu", torch.float32)
+        vals = (eigdata[t]["eigval"].detach().to("cpu", torch.float32) if evals is None
+                else torch.from_numpy(evals[t]).to(torch.float32)).reshape(-1)
+        vecs[j] = vec
+        for k in rows:
+            for e in variants[k].evs:
+                w[j, k, int(e) - 1] += float(variants[k].amount) * vals[int(e) - 1].sqrt()
+    return vecs, w
+
+
 class LoopPlumbing:
     """What the device-resident loop engines share (this module's EditEngine, stable_audio.StableAudioEditEngine): an LRU
     of loop plans (persistent buffers + tapes + one instantiated hipGraph per loop shape) and the graph runner.
@@ -635,12 +742,14 @@ class EditEngine(LoopPlumbing):
     MAX_VARIANTS = 16       # rows per edit_variants / edit_clips call (U-Net batch <= 32); variants.py and batch.py chunk
 
     def _variant_loop(self, tag, order, segs, tgt, neg, cfgs, eta, noise_ok, fill_noise, join_rows, use_graph, src=None,
-                      n_tables=0):
+                      n_tables=0, drift=None, n_steps=None):
         """The segmented loop of edit_variants and edit_clips.  order / segs: variant_plan's; tgt / neg / cfgs: per row in
         the caller's order; fill_noise(buf) loads the plan's noise buffer, join_rows(seg) returns the x_t rows that start
-        at a segment.  src (the table of every row, caller's order) with n_tables makes the noise buffer
-        [n_tables, Z0, H, W, C] and the step op read table src[row]; without it the one table [Z0, H, W, C] is shared.
-        Returns the rows [K, H, W, C] in the caller's order."""
+        at a segment from (segment, the loop's row buffer).  src (the table of every row, caller's order) with n_tables makes
+        the noise buffer [n_tables, Z0, H, W, C] and the step op read table src[row]; without it the one table
+        [Z0, H, W, C] is shared.  drift (drift_variants: dict(vecs [S, n_ev, H, W, C], w [S, K, n_ev] in the caller's row
+        order, s_first, shift_np, mask, fix_alpha, par, fix_mode)) makes the step op the PC drift step.  n_steps stops the
+        loop after that many steps.  Returns the rows [K, H, W, C] in the caller's order."""
         s = self.sched
         T = s.num_inference_steps
         K = len(order)
@@ -652,8 +761,10 @@ class EditEngine(LoopPlumbing):
         groups_all = [neg[v] for v in order] + [tgt[v] for v in order]
         L0, L1 = self._ctx_lens(groups_all)
         tables = () if src is None else (n_tables,)
+        dkey = () if drift is None else (tuple(drift["vecs"].shape[:2]), drift["s_first"], bool(drift["shift_np"]),
+                                          drift["fix_mode"], float(drift["fix_alpha"]))
         key = (tag, K, *tables, T, tuple(sg["tstart"] for sg in segs), tuple(sg["a"] for sg in segs), L0, L1, v_pred,
-               has_noise, tuple(self._arith_for(2 * sg["a"]) for sg in segs))
+               has_noise, tuple(self._arith_for(2 * sg["a"]) for sg in segs), *dkey)
         plan = self._get_plan(key)
         if plan is None:
             plan = self._plans[key] = dict(
@@ -663,6 +774,12 @@ class EditEngine(LoopPlumbing):
                 coef=torch.zeros((Z0, L.COEF_STRIDE), device=self.device, dtype=torch.float32),
                 cfg=torch.zeros(K, device=self.device, dtype=torch.float32),
                 src=None if src is None else torch.zeros(K, device=self.device, dtype=torch.int32), segs=[])
+            if drift is not None:
+                S, n_ev = drift["vecs"].shape[:2]
+                dev_buf = lambda *shape: torch.zeros(shape, device=self.device, dtype=torch.float32)      # noqa: E731
+                plan.update(vecs=dev_buf(S, n_ev, self.H, self.W, self.C), w=dev_buf(S, K, n_ev),
+                            mask=dev_buf(self.H, self.W, self.C) if drift["fix_mode"] else None,
+                            par=dev_buf(T + 1, self.H, self.W, self.C) if drift["fix_mode"] == 1 else None)
             for sg in segs:
                 a = sg["a"]
                 eng = self.unet(2 * a, L0, L1, share=1)
@@ -670,9 +787,15 @@ class EditEngine(LoopPlumbing):
                 for blk in range(2):
                     pre.copy2d(plan["cur"], eng.x_in[blk * a:(blk + 1) * a], rows=1, cols=a * numel, ld_src=a * numel,
                                ld_dst=a * numel, name="x_in<-x_t")
-                post.step_variants(cur=plan["cur"], zs=plan["zs"] if has_noise else None, eps=eng.eps[:2 * a],
-                                   cfg=plan["cfg"], coef=plan["coef"], state=plan["state"], numel=numel, a=a, Z=Z0,
-                                   v_pred=v_pred, src=plan["src"], N=n_tables)
+                step = dict(cur=plan["cur"], zs=plan["zs"] if has_noise else None, eps=eng.eps[:2 * a], cfg=plan["cfg"],
+                            coef=plan["coef"], state=plan["state"], numel=numel, a=a, Z=Z0, v_pred=v_pred)
+                if drift is None:
+                    post.step_variants(**step, src=plan["src"], N=n_tables)
+                else:       # the stored trajectory's x_{t-1} of loop step s is its point s + 1 (main_pc_apply_drift.py:153)
+                    post.drift_step_variants(**step, vecs=plan["vecs"], w=plan["w"], n_ev=n_ev, a_max=K,
+                                             s_first=drift["s_first"], S=S, shift_np=drift["shift_np"], mask=plan["mask"],
+                                             par=plan["par"], fix_mode=drift["fix_mode"], par_off=1,
+                                             fix_alpha=float(drift["fix_alpha"]))
                 post.advance(plan["state"])
                 pre.finalize()
                 post.finalize()
@@ -684,22 +807,34 @@ class EditEngine(LoopPlumbing):
         plan["cfg"].copy_(torch.tensor([float(cfgs[v]) for v in order], dtype=torch.float32))
         if src is not None:
             plan["src"].copy_(torch.tensor([src[v] for v in order], dtype=torch.int32))
+        if drift is not None:
+            plan["vecs"].copy_(drift["vecs"])
+            plan["w"].copy_(drift["w"][:, list(order)])
+            if drift["fix_mode"]:
+                plan["mask"].copy_(drift["mask"])
+            if drift["fix_mode"] == 1:
+                plan["par"].copy_(drift["par"])
         self._upload_timesteps(s.timesteps, T)
         for sg, sp in zip(segs, plan["segs"]):
             a = sg["a"]
             self._set_cond(sp["eng"], groups_all[:a] + groups_all[K:K + a])
             self._patch_time(sp["eng"], self.ts_dev, 1, 2 * a, offset=T - Z0, state=plan["state"])
         plan["state"].zero_()
+        left = None if n_steps is None else max(0, int(n_steps))
         for sg, sp in zip(segs, plan["segs"]):
             lo, hi = sg["join"]
-            cur[lo:hi].copy_(join_rows(sg))                            # inversion_utils.py:203, per row
+            cur[lo:hi].copy_(join_rows(sg, cur))                       # inversion_utils.py:203, per row
             eng, pre, post = sp["eng"], sp["pre"], sp["post"]
+            steps = sg["steps"] if left is None else min(sg["steps"], left)
+            left = None if left is None else left - steps
+            if steps == 0:
+                continue
 
             def body(eng=eng, pre=pre, post=post):
                 pre.run()
                 eng.tape.run()
                 post.run()
-            self._run_graph(body, sg["steps"], use_graph, sp)
+            self._run_graph(body, steps, use_graph, sp)
         return cur[variant_positions(order)]                       # advanced indexing: a copy, in the caller's order
 
     @torch.inference_mode()
@@ -727,7 +862,7 @@ class EditEngine(LoopPlumbing):
         return self._variant_loop(
             "variants", order, segs, tgt, neg, cfg_tars, eta, zs is not None,
             fill_noise=lambda buf: buf.copy_(zs[:buf.shape[0], 0]),
-            join_rows=lambda sg: xts[sg["tstart"], 0].expand(sg["join"][1] - sg["join"][0], -1, -1, -1),
+            join_rows=lambda sg, cur: xts[sg["tstart"], 0].expand(sg["join"][1] - sg["join"][0], -1, -1, -1),
             use_graph=use_graph)
 
     # ------------------------------------------------------------------ edits of many inversions
@@ -753,8 +888,75 @@ class EditEngine(LoopPlumbing):
         return self._variant_loop(
             "clips", order, segs, tgt, neg, [r[4] for r in rows], eta, True,
             fill_noise=lambda buf: clip_noise_fill(buf, zs_list),
-            join_rows=lambda sg: clip_join_rows(xts_list, clips, tstarts, order, sg),
+            join_rows=lambda sg, cur: clip_join_rows(xts_list, clips, tstarts, order, sg),
             use_graph=use_graph, src=clips, n_tables=len(xts_list))     # clips: validated in clip_plan, all < N
+
+    # ------------------------------------------------------------------ K principal-component drifts of one trajectory
+    MAX_DRIFT_VARIANTS = 15     # variants per drift_variants call; with the trunk row the U-Net batch stays <= 32
+
+    @torch.inference_mode()
+    def drift_variants(self, x_T, zs, variants, cond_tgt, cond_neg, cfg_tar, eta, vec_table, weight_table, *,
+                       shift_x0_for_np=True, mask=None, fix_alpha=None, par_xts=None, use_graph=True, n_steps=None):
+        """K principal-component drifts of ONE recorded trajectory in one device-resident loop.  Variant v is
+        main_pc_apply_drift.apply_pcs with combine_evs on its own PC set, amount and window: all T steps from x_T
+        [1, H, W, C] with the recorded noise zs [T, 1, H, W, C] (edit()'s order: step s adds zs[T - s - 1]) under the one
+        prompt pair cond_tgt / cond_neg (one-row Conditioning) and guidance cfg_tar; eta is 0 or 1.  variants: objects
+        with drift_start / drift_end (or such pairs).  vec_table [S, n_ev, H, W, C] and weight_table [S, K, n_ev] (the
+        caller's variant order) cover the loop steps drift_union(variants, T); drift_tables builds them.
+
+        Row 0 of the loop is the undrifted trunk; the variants run sorted by drift_start, largest first, and a row joins
+        as a copy of the trunk at the first step of its window (drift_plan), so the trunk's steps are computed once for
+        all of them: U-Net batch 2 * (1 + joined rows).  fix_alpha (with mask [H, W, C]) blends every drifted step towards
+        the undrifted parallel trajectory outside the mask: par_xts [T + 1, 1, H, W, C] (the file's stored points) when
+        given, else the trunk row.  The blend goes with the drift: a row whose weights are all zero at a step (amount 0, or
+        only zero eigenvalues) is neither drifted nor blended there, where apply_pcs would still blend it; apply_pcs_grid
+        refuses amount 0 together with fix_alpha.  n_steps stops after that many loop steps (rows that have not joined are the trunk).
+        Returns the latents [K, H, W, C] in the caller's order."""
+        if self.kind not in ("audioldm", "audioldm2", "tango"):
+            raise ValueError(f"drift_variants: engine kind {self.kind!r} is not supported (AudioLDM, AudioLDM2, TANGO)")
+        T = self.sched.num_inference_steps
+        variants = list(variants)
+        order, segs = drift_plan(variants, T, self.MAX_DRIFT_VARIANTS)
+        K = len(variants)
+        eta = float(eta)
+        if eta not in (0.0, 1.0):
+            raise ValueError(f"drift_variants: eta {eta:g} is not supported: the recorded step (scheduler.step, variance "
+                             f"eta^2 * var) and the loop's coefficient rows (eta * var) agree only for eta 0 and 1")
+        s_first, S = drift_union(variants, T)
+        lat = (self.H, self.W, self.C)
+        if vec_table.dim() != 5 or vec_table.shape[0] != S or tuple(vec_table.shape[2:]) != lat or \
+                not 1 <= vec_table.shape[1] <= MAX_DRIFT_EV:
+            raise ValueError(f"drift_variants: vec_table {tuple(vec_table.shape)}, expected [S = {S}, n_ev <= {MAX_DRIFT_EV}, "
+                             f"H, W, C = {list(lat)}] for the loop steps {s_first}..{s_first + S - 1}")
+        if tuple(weight_table.shape) != (S, K, vec_table.shape[1]):
+            raise ValueError(f"drift_variants: weight_table {tuple(weight_table.shape)}, expected "
+                             f"{[S, K, vec_table.shape[1]]} ([S, variants, n_ev])")
+        if zs is not None and (zs.shape[0] != T or zs.numel() != T * math.prod(lat)):
+            raise ValueError(f"drift_variants: zs {tuple(zs.shape)} is not the trajectory's T = {T} noise maps")
+        if x_T.numel() != math.prod(lat):
+            raise ValueError(f"drift_variants: x_T {tuple(x_T.shape)} is not ONE latent [1, H, W, C] = {[1, *lat]}")
+        fix_mode = 0
+        if fix_alpha is not None:
+            if mask is None or tuple(mask.shape[-3:]) != lat or mask.numel() != math.prod(lat):
+                raise ValueError("drift_variants: fix_alpha needs a mask [H, W, C]")
+            if par_xts is not None and (par_xts.shape[0] != T + 1 or par_xts.numel() != (T + 1) * math.prod(lat)):
+                raise ValueError(f"drift_variants: par_xts {tuple(par_xts.shape)} is not the trajectory's T + 1 = {T + 1} points")
+            fix_mode = 1 if par_xts is not None else 2
+        tgt, neg = _variant_rows(cond_tgt, 1, "cond_tgt") * (K + 1), _variant_rows(cond_neg, 1, "cond_neg") * (K + 1)
+        w_rows = torch.cat([torch.zeros_like(weight_table[:, :1]), weight_table], 1)       # row 0: the trunk never drifts
+        drift = dict(vecs=vec_table, w=w_rows, s_first=s_first, shift_np=bool(shift_x0_for_np), fix_mode=fix_mode,
+                     fix_alpha=0.0 if fix_alpha is None else float(fix_alpha),
+                     mask=None if not fix_mode else mask.reshape(lat),
+                     par=None if fix_mode != 1 else par_xts.reshape(T + 1, *lat))
+        x_T = x_T.reshape(1, *lat)
+
+        def join(sg, cur):                      # the first segment starts from x_T, later rows copy the trunk row
+            return (x_T if sg["start"] == 0 else cur[0:1]).expand(sg["join"][1] - sg["join"][0], -1, -1, -1)
+        out = self._variant_loop(
+            "drift", [0] + [1 + v for v in order], segs, tgt, neg, [float(cfg_tar)] * (K + 1), eta, zs is not None,
+            fill_noise=lambda buf: buf.copy_(zs.reshape(T, *lat)), join_rows=join, use_graph=use_graph, drift=drift,
+            n_steps=n_steps)
+        return out[1:]
 
     # ------------------------------------------------------------------ A16: DDIM baseline
     @torch.inference_mode()

@@ -514,6 +514,21 @@ class Tape:
                   [0.0, *c_imm], [cur, zs, eps, src, cfg, coef, state, out], name=name,
                   nbytes=4 * numel * (4 * a + has_noise * (1 if src is None else a)))
 
+    def drift_step_variants(self, *, cur, zs, eps, cfg, coef, state, numel, a, Z, vecs, w, n_ev, a_max, s_first, S,
+                            v_pred=0, shift_np=True, mask=None, par=None, fix_mode=0, par_off=0, fix_alpha=0.0, s_imm=0,
+                            c_imm=(0, 0, 0, 0, 0), s_mul=1, s_off=0, name="drift_step_variants"):
+        """step_variants for the `a` principal-component drift rows in rows [0, a) of cur [K, numel], in place
+        (AED_OP_DRIFT_STEP_VARIANTS): loop steps [s_first, s_first + S) read the directions vecs [S, n_ev, numel] and the
+        weights w [S, a_max, n_ev]; a row with a non-zero weight drifts, every other row takes step_variants' arithmetic.
+        fix_mode 1 blends towards row `step + par_off` of the table par [*, numel], 2 towards the stepped row 0, both
+        outside mask [numel] with weight fix_alpha; 0 does not blend."""
+        has_noise = int(zs is not None)
+        self._add(L.OP_DRIFT_STEP_VARIANTS,
+                  [numel & 0xFFFFFFFF, numel >> 32, a, Z if has_noise else 0, s_imm, v_pred, has_noise, s_mul, s_off, n_ev,
+                   a_max, s_first, S, int(bool(shift_np)), fix_mode, par_off],
+                  [fix_alpha, *c_imm], [cur, zs, eps, vecs, cfg, coef, state, w, mask, par], name=name,
+                  nbytes=4 * numel * (4 * a + has_noise + n_ev + 2 * int(fix_mode > 0)))
+
     # ------------------------------------------------------------------ Stable Audio Open ops (csrc/stable_audio.hip)
     def rotary(self, x, cos, sin, *, M, N, H, D, R, ld=None, nsec=2, sec_stride=None, name="rotary"):
         """Rotate the first R features of every head of q (and k) inside a fused projection buffer x[M, ld], in place."""

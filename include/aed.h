@@ -97,6 +97,12 @@ enum aed_opcode {
                                  cfg_scalar = cfg[v] (EditEngine.edit_variants).  With a device int[a] `src` (slot p3) and N
                                  tables zs [N][Z][numel] the rows belong to up to N inversions and row v reads table src[v]
                                  (EditEngine.edit_clips); without src the op is unchanged                                  */
+    AED_OP_DRIFT_STEP_VARIANTS = 29, /* one step of `a` principal-component drift variants that replay ONE recorded trajectory:
+                                 opcode 28's CFG combine and step with the recorded noise, then, for a row with a non-zero
+                                 weight at this loop step, apply_drift (pc_drift.py:201-278) along sum_e w[step][row][e] *
+                                 vecs[step][e] and the optional fix_alpha blend towards the undrifted parallel trajectory (a
+                                 table indexed by loop step, or row 0 of the launch), in place.  A row whose weights are all
+                                 zero is bit-identical to opcode 28 (EditEngine.drift_variants)                             */
     AED_OP_COUNT
 };
 
@@ -207,6 +213,22 @@ int aed_reverse_step_variants(const float* xt, const float* eps, const float* cf
  * (xt[v], {eps[v], eps[n_rows + v]}, cfg[v], 1 variant, z[v]).                                                          */
 int aed_reverse_step_clips(const float* xt, const float* eps, const float* cfg, int n_rows, const float* coef_host,
                            int v_prediction, const float* z, float* prev_out, int64_t numel, void* stream);
+
+/* aed_reverse_step_variants followed by the principal-component drift of pc_drift.py:201-278, one launch, IN PLACE on
+ * xt [n_rows][numel]: eps, cfg, coef_host, z as above; vecs [n_ev][numel] are the PC directions of this timestep and
+ * w: DEVICE float[n_rows][n_ev] the weights amount * sqrt(lambda_e) (0 for a PC a row does not use).  Per element a row
+ * with a non-zero weight computes, in fp32 and this order,
+ *   shift = sum_e w[row][e] * vecs[e]              (ascending e)
+ *   mean = prev - c4*z (with z)   eps_hat = (mean - c2*x0)/c3 [- (c1/c0)*shift when shift_x0_for_np]
+ *   prev = c2*(x0 + shift) + c3*eps_hat [+ c4*z]
+ *   fix_mode != 0:  prev = mask*prev + (1 - mask)*(fix_alpha*par + (1 - fix_alpha)*prev)
+ * where (x0, prev) is the plain step's pair.  fix_mode 0: no blend; 1: par = parallel [numel]; 2: par = row 0's stepped
+ * value (row 0 must have zero weights).  A row whose weights are all zero is bit-identical to aed_reverse_step_variants.
+ * Refused: null pointers, n_rows < 1, n_ev outside [1, 8], fix_mode != 0 without mask, fix_mode 1 without parallel.   */
+int aed_drift_step_variants(float* xt, const float* eps, const float* cfg, int n_rows, const float* coef_host,
+                            int v_prediction, const float* z, const float* vecs, const float* w, int n_ev,
+                            int shift_x0_for_np, const float* mask, const float* parallel, int fix_mode, float fix_alpha,
+                            int64_t numel, void* stream);
 
 /* PipelineWrapper.sample_xts_from_x0 inner statement (models.py:81):
  * out = x0*sqrt_abar + noise*sqrt_1m_abar, for n_t rows (noise drawn by the host RNG).      */
