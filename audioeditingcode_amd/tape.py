@@ -399,11 +399,11 @@ class Tape:
         a_target = max(1, (GN_APPLY_BLOCKS_PER_CU * CU_COUNT) // max(1, B))
         a_rpc = max(16, math.ceil(HW / a_target))       # (>= 16 rows per block: every block first re-reduces the batch item's partials)
         a_chunks = math.ceil(HW / a_rpc)
-        part = self.alloc(B, s_chunks, G, 2)
+        part = self.alloc(B, s_chunks, G, 3)        # (shift, sum, sumsq about the shift) per slab and group
         nb = 4 * B * HW * C
         self._add(L.OP_GN_STATS, [B, HW, C, G, ldx, s_rpc, s_chunks, C1, ldx2], [], [x, part, x2],
                   name=name + ".stats", nbytes=nb)
-        self._add(L.OP_GN_APPLY, [B, HW, C, G, ldx, a_rpc, s_chunks, act, ldy, a_chunks, C1, ldx2], [eps],
+        self._add(L.OP_GN_APPLY, [B, HW, C, G, ldx, a_rpc, s_chunks, act, ldy, a_chunks, C1, ldx2, s_rpc], [eps],
                   [x, part, gamma, beta, out, x2], name=name + ".apply", nbytes=2 * nb)
         return out
 
