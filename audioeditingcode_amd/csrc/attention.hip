@@ -429,7 +429,7 @@ static int launch_t(const AttnParams& p, int B, hipStream_t s) {
 // slots: p0=q p1=k p2=v p3=bias(or null) p4=out
 //        i0=B i1=H i2=Nq i3=Nk i4=D i5=ldq i6=ldk i7=ldv i8=ldo i9=ld_bias
 //        i10=bsq i11=bsk i12=bsv i13=bso (elements) i14=variant (0 auto: transposed-score kernel when Nk > 64; 1 forces the single-pass kernel;
-//        3 forces the split-bf16 kernel) ; f0=scale
+//        3 forces the split-bf16 kernel, 4 its reference body) ; f0=scale
 int launch_attention(const aed_op* op, hipStream_t s) {
     const int32_t* i = op->i;
     AttnParams p;
@@ -443,7 +443,9 @@ int launch_attention(const aed_op* op, hipStream_t s) {
     AED_REQUIRE(p.ldq % 4 == 0 && p.ldk % 4 == 0 && p.ldv % 4 == 0, "attention: row strides must be multiples of 4");
     AED_REQUIRE(p.Nq > 0 && p.Nk > 0, "attention: empty sequence");
     AED_REQUIRE(p.ldo % 4 == 0, "attention: output row stride must be a multiple of 4");
-    if (p.Nk > KV_TILE && i[14] != 1) {
+    // variants 3 / 4 force the split-bf16 kernel (tests and tools; the tapes ask for 3 only with Nk > 64), short key sequences too
+    const bool forced = i[14] == 3 || i[14] == 4;
+    if ((p.Nk > KV_TILE && i[14] != 1) || forced) {
         // transposed-score kernel.  Few workgroups (U-Net batch 2):
         // the 4 waves of a workgroup split the keys; many: each wave takes its own query tile.
         const long wg_ksplit1 = (long)aed_cdiv(p.Nq, 128) * p.H * i[0];
@@ -451,10 +453,11 @@ int launch_attention(const aed_op* op, hipStream_t s) {
         int rc = 0;
         // flag bit 2 (tapes built under tape.arith_mode("bf16x6")): the throughput-regime kernel on split-bf16 MFMAs
         // (attention_x6.hip) for the head dims it takes; variant 3 forces it whatever the grid size (tests)
-        if (((op->flags & 4) && !ks4) || i[14] == 3) {
-            rc = launch_attention_x6(p, i[0], i[4], s);
+        // Variant 4 (tests and tools/attn_x6_diet_ab.py only) runs its reference body.
+        if (((op->flags & 4) && !ks4) || forced) {
+            rc = launch_attention_x6(p, i[0], i[4], i[14] == 4, s);
             if (rc >= 0) return rc;
-            AED_REQUIRE(i[14] != 3, "attention: the split-bf16 kernel does not take head dim %d / these operands", i[4]);
+            AED_REQUIRE(!forced, "attention: the split-bf16 kernel does not take head dim %d / these operands", i[4]);
         }
         switch (i[4]) {
             case 32: rc = ks4 ? launch_t<32, 4>(p, i[0], s) : launch_t<32, 1>(p, i[0], s); break;

@@ -63,8 +63,277 @@ __device__ __forceinline__ void ax6_mfma6(af32x16& acc, const abf16x8 (&a)[3], c
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The product kernel.  Same pieces, same six products in the same order, same max / exp / sum order as
+// attention_x6_ref_kernel below (every output value is bit-identical to it); what differs is the vector-instruction count
+// around the MFMAs (census and measurements: profiles/attn_x6_valu_diet.md; -35 % vector instructions, 6-14 % of the time):
+//   * K, V and the key bias come through buffer loads.  A thread's byte offsets inside a tile are computed ONCE; moving to
+//     the next tile advances the descriptor's base and shrinks its num_records in SGPRs.  num_records ends with the last
+//     valid key row of this head, so keys >= Nk and the dead prefetches past the last tile read 0 (they are masked to -inf
+//     and their probabilities are 0: the output does not change) and nothing is clamped per lane.  The whole per-lane
+//     offset stays in the vector offset, as in conv_gemm_x6.hip (the scalar offset operand is not relied on for the range
+//     check); the launcher falls back to the reference kernel when a span does not fit 31 bits.
+//   * the tiles with k0 + 32 <= Nk run without any mask code; the ragged tile and the dead tile of an odd count are a tail.
+// The 16 D loader items of a tile (8 D K items: one float4; 8 D V items: 4 keys x 1 channel) are dealt to the 256 threads in
+// that order, so a register slot of a wave holds a K item or a V item (8 D is a multiple of 64), never both.
+// (Measured and NOT here, profiles/attn_x6_valu_diet.md: a wave-uniform branch around the accumulator rescale when no lane's
+// maximum moved -- slower by 1-2 % at three of five settings; an 8-wave workgroup that stages K / V once per 256 queries --
+// never faster than this one and 15 % slower at 256 tokens.)
+typedef float af32x4 __attribute__((ext_vector_type(4)));
+template <int V> struct ax6_c { static constexpr int value = V; };
+
 template <int D>
 __global__ __launch_bounds__(256, 2) void attention_x6_kernel(AttnParams p) {
+    constexpr int NT = 256;                        // threads
+    constexpr int NDB = D / 16;                    // 16-wide d blocks of the S^T contraction
+    constexpr int DT = (D + 31) / 32;              // 32-row tiles of O^T
+    constexpr int KQ = NDB * 3 * 64;               // uint4 per K stage ([db][piece][key 32][h 2] x 16 B)
+    constexpr int VQ = 2 * 3 * DT * 64;            // uint4 per V stage ([kb][piece][dt][d 32][h 2] x 16 B)
+    constexpr int STAGE = KQ + VQ;
+    constexpr int C4 = D / 4;                      // float4 per K row
+    constexpr int NI = (16 * D + NT - 1) / NT;     // loader items per thread: items [0, 8 D) are K, [8 D, 16 D) are V
+    static_assert(D % 16 == 0 && 2 * STAGE * 16 <= 65536, "head dim");
+    __shared__ uint4 lds[2 * STAGE];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fi = lane & 31, fh = lane >> 5;
+    // XCD-aware order (attention.hip): the query tiles of one (batch, head) run on one XCD
+    int qt, head, b;
+    {
+        const unsigned nx = gridDim.x, ny = gridDim.y, nwg = nx * ny * gridDim.z;
+        const unsigned orig = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
+        const unsigned xcd = orig & 7u, q = nwg >> 3, r = nwg & 7u;
+        const unsigned id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+        qt = (int)(id % nx);
+        head = (int)((id / nx) % ny);
+        b = (int)(id / (nx * ny));
+    }
+    const int q0 = qt * 128 + wave * 32;
+    const int hoff = head * D;
+    const float* Q = p.q + (size_t)b * p.bsq + hoff;
+
+    // Q^T pieces (B operand of S^T): lane (query fi, half fh) holds Q[q0 + fi][16 db + 8 fh + e], pre-scaled
+    abf16x8 qp[NDB][3];
+    {
+        const float* qrow = Q + (size_t)min(q0 + fi, p.Nq - 1) * p.ldq + 8 * fh;
+#pragma unroll
+        for (int db = 0; db < NDB; ++db) {
+            const float4 a = *reinterpret_cast<const float4*>(qrow + 16 * db);
+            const float4 c = *reinterpret_cast<const float4*>(qrow + 16 * db + 4);
+            const float x[8] = {a.x * p.scale, a.y * p.scale, a.z * p.scale, a.w * p.scale,
+                                c.x * p.scale, c.y * p.scale, c.z * p.scale, c.w * p.scale};
+            ax6_split8(x, qp[db]);
+        }
+    }
+    af32x16 oacc[DT];
+#pragma unroll
+    for (int c = 0; c < DT; ++c)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[c][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;          // l_run: this lane's 16-key share; the halves are added at the end
+
+    const int ntiles = (p.Nk + 31) / 32;
+    // what loader item i of this wave is (compile-time wherever all waves agree)
+    auto is_k = [&](int i) { return NT * (i + 1) <= 8 * D ? true : NT * i >= 8 * D ? false : wave * 64 + NT * i < 8 * D; };
+    auto is_v = [&](int i) {
+        return NT * (i + 1) <= 8 * D ? false : (NT * i >= 8 * D && NT * (i + 1) <= 16 * D) ? true
+                                             : (wave * 64 + NT * i >= 8 * D && wave * 64 + NT * i < 16 * D);
+    };
+    // byte offsets inside a tile, fixed for the whole key loop (K items use [0]; V items one per key)
+    unsigned off[NI][4];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int item = tid + NT * i;
+        if (is_k(i)) {
+            off[i][0] = 4u * (unsigned)((item / C4) * p.ldk + 4 * (item % C4));
+            off[i][1] = off[i][2] = off[i][3] = 0u;
+        } else {
+            const int it = item - 8 * D, kg = it / D, d = it - kg * D;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) off[i][j] = 4u * (unsigned)((4 * kg + j) * p.ldv + d);
+        }
+    }
+    // descriptors of the NEXT tile to prefetch: base at its first key row, num_records up to the end of key row Nk - 1
+    const char* kbase = reinterpret_cast<const char*>(p.k + (size_t)b * p.bsk + hoff);
+    const char* vbase = reinterpret_cast<const char*>(p.v + (size_t)b * p.bsv + hoff);
+    const int kstep = 128 * p.ldk, vstep = 128 * p.ldv;                   // bytes per 32-key tile
+    int krem = 4 * ((p.Nk - 1) * p.ldk + D), vrem = 4 * ((p.Nk - 1) * p.ldv + D);
+    const __amdgpu_buffer_rsrc_t srd_b = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(p.bias ? p.bias + (size_t)b * p.ld_bias : p.k), 0, p.bias ? 4 * p.Nk : 0, 0x00020000);
+
+    af32x4 reg[2][NI];
+    auto prefetch = [&](af32x4 (&rg)[NI]) {        // tiles are prefetched in order: each call takes the next one
+        const __amdgpu_buffer_rsrc_t srd_k = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, krem, 0x00020000);
+        const __amdgpu_buffer_rsrc_t srd_v = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, 0, vrem, 0x00020000);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            if (is_k(i)) {
+                rg[i] = __builtin_bit_cast(af32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_k, off[i][0], 0, 0));
+            } else if (is_v(i)) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    rg[i][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(srd_v, off[i][j], 0, 0));
+            }
+        }
+        kbase += kstep; krem = max(krem - kstep, 0);
+        vbase += vstep; vrem = max(vrem - vstep, 0);
+    };
+    auto stage_write = [&](uint4* st, const af32x4 (&rg)[NI]) {
+        uint2* k2 = reinterpret_cast<uint2*>(st);
+        uint2* v2 = reinterpret_cast<uint2*>(st + KQ);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int item = tid + NT * i;
+            unsigned h0, m0, l0, h1, m1, l1;
+            if (is_k(i)) {
+                const int key = item / C4, c4 = item % C4;
+                ax6_split_pair(rg[i][0], rg[i][1], h0, m0, l0);
+                ax6_split_pair(rg[i][2], rg[i][3], h1, m1, l1);
+                // K[key][4 c4 + j]: d block c4 >> 2, lane half (c4 >> 1) & 1, e = 4 (c4 & 1) + j
+                uint2* dst = k2 + ((c4 >> 2) * 3 * 32 + key) * 4 + ((c4 >> 1) & 1) * 2 + (c4 & 1);
+                dst[0] = make_uint2(h0, h1);
+                dst[32 * 4] = make_uint2(m0, m1);
+                dst[2 * 32 * 4] = make_uint2(l0, l1);
+            } else if (is_v(i)) {
+                const int it = item - 8 * D, kg = it / D, d = it - kg * D;
+                ax6_split_pair(rg[i][0], rg[i][1], h0, m0, l0);
+                ax6_split_pair(rg[i][2], rg[i][3], h1, m1, l1);
+                // keys 4 kg + j of channel d: key block kg >> 2, g = kg & 3 -> lane half g & 1, e = 4 (g >> 1) + j
+                const int kb = kg >> 2, g = kg & 3;
+                uint2* dst = v2 + (((kb * 3) * DT + (d >> 5)) * 32 + (d & 31)) * 4 + (g & 1) * 2 + (g >> 1);
+                dst[0] = make_uint2(h0, h1);
+                dst[DT * 32 * 4] = make_uint2(m0, m1);
+                dst[2 * DT * 32 * 4] = make_uint2(l0, l1);
+            }
+        }
+    };
+    if constexpr (DT * 32 > D) {                   // rows d >= D of V^T are never staged: keep them zero (both stages)
+        for (int e = tid; e < 2 * STAGE; e += NT) lds[e] = make_uint4(0u, 0u, 0u, 0u);
+        __syncthreads();
+    }
+
+    // one key tile; u: LDS stage and register slot (static), MASKED: the tile may be ragged or dead
+    auto tile = [&](auto uc, auto mc, const int t) {
+        constexpr int u = decltype(uc)::value;
+        constexpr bool MASKED = decltype(mc)::value != 0;
+        const uint4* st = lds + u * STAGE;
+        // ---- S^T tile: 32 keys x 32 queries
+        af32x16 sacc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
+#pragma unroll
+        for (int db = 0; db < NDB; ++db) {
+            abf16x8 kf[3];
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) kf[pl] = __builtin_bit_cast(abf16x8, st[((db * 3 + pl) * 32 + fi) * 2 + fh]);
+            ax6_mfma6(sacc, kf, qp[db]);
+        }
+        // tile t+1 -> the other stage (its readers finished before the last barrier), then refill the slot with tile t+3
+        stage_write(lds + (u ^ 1) * STAGE, reg[u ^ 1]);
+        prefetch(reg[u ^ 1]);
+        // sacc[r] = S[key k0 + (r&3) + 8*(r>>2) + 4*fh][query fi]
+        const int k0 = t * 32;
+        if (p.bias) {                              // keys >= Nk read 0 and are masked below
+            const unsigned bo = 4u * (unsigned)(k0 + 4 * fh);
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    sacc[4 * rq + e] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(srd_b, bo + 4u * (8 * rq + e), 0, 0));
+        }
+        if constexpr (MASKED) {
+            if (k0 + 32 > p.Nk) {                  // ragged last tile / dead tile (wave-uniform)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (k0 + (r & 3) + 8 * (r >> 2) + 4 * fh >= p.Nk) sacc[r] = -INFINITY;
+            }
+        }
+        float mx = sacc[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sacc[r]);
+        {
+            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
+            mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));       // the other 16 keys of this query
+        }
+        const float mn = fmaxf(m_run, mx);
+        const float alpha = __expf(m_run - mn);
+        m_run = mn;
+        float rsum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            sacc[r] = __expf(sacc[r] - mn);
+            rsum += sacc[r];
+        }
+        l_run = l_run * alpha + rsum;
+#pragma unroll
+        for (int c = 0; c < DT; ++c)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) oacc[c][r] *= alpha;
+        // ---- O^T += V^T P^T: registers 8 kb .. 8 kb + 7 are the B operand of key block kb
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            abf16x8 pf[3];
+            const float x[8] = {sacc[8 * kb], sacc[8 * kb + 1], sacc[8 * kb + 2], sacc[8 * kb + 3],
+                                sacc[8 * kb + 4], sacc[8 * kb + 5], sacc[8 * kb + 6], sacc[8 * kb + 7]};
+            ax6_split8(x, pf);
+#pragma unroll
+            for (int c = 0; c < DT; ++c) {
+                abf16x8 vf[3];
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl)
+                    vf[pl] = __builtin_bit_cast(abf16x8, st[KQ + (((kb * 3 + pl) * DT + c) * 32 + fi) * 2 + fh]);
+                ax6_mfma6(oacc[c], vf, pf);
+            }
+        }
+        __syncthreads();
+    };
+
+    prefetch(reg[0]);
+    prefetch(reg[1]);
+    stage_write(lds, reg[0]);
+    prefetch(reg[0]);
+    __syncthreads();
+    // two tiles per trip (static register slots).  Main loop: both tiles are full, no mask code; tail: the last one or two
+    // tiles, ragged or not, and the dead tile of an odd count (fully masked, adds nothing)
+    const int nmain = (p.Nk / 32) & ~1;
+    int t0 = 0;
+    for (; t0 < nmain; t0 += 2) {
+        tile(ax6_c<0>{}, ax6_c<0>{}, t0);
+        tile(ax6_c<1>{}, ax6_c<0>{}, t0 + 1);
+    }
+    if (t0 < ntiles) {
+        tile(ax6_c<0>{}, ax6_c<1>{}, t0);
+        tile(ax6_c<1>{}, ax6_c<1>{}, t0 + 1);
+    }
+
+    // ---- finish: add the two lane halves' shares of l, normalise, store O[q][d] (4 consecutive d per register quad)
+    {
+        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
+        l_run = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+    }
+    const float inv = 1.0f / l_run;
+    const int qr = q0 + fi;
+    if (qr < p.Nq) {
+        float* O = p.o + (size_t)b * p.bso + hoff + (size_t)qr * p.ldo;
+#pragma unroll
+        for (int c = 0; c < DT; ++c)
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq) {
+                const int d0 = c * 32 + 8 * rq + 4 * fh;
+                if (d0 < D)
+                    *reinterpret_cast<float4*>(O + d0) = make_float4(oacc[c][4 * rq] * inv, oacc[c][4 * rq + 1] * inv,
+                                                                     oacc[c][4 * rq + 2] * inv, oacc[c][4 * rq + 3] * inv);
+            }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The kernel as it was before the changes above, kept compiled as the bit reference of the product kernel (variant 4 of the
+// attention record: tests/test_gpu_attention_x6_diet.py, tools/attn_x6_diet_ab.py) and as the path for operands whose
+// span does not fit the 31-bit buffer offsets.  The engines never select it.
+template <int D>
+__global__ __launch_bounds__(256, 2) void attention_x6_ref_kernel(AttnParams p) {
     constexpr int NDB = D / 16;                    // 16-wide d blocks of the S^T contraction
     constexpr int DT = (D + 31) / 32;              // 32-row tiles of O^T
     constexpr int KQ = NDB * 3 * 64;               // uint4 per K stage ([db][piece][key 32][h 2] x 16 B)
@@ -276,19 +545,30 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(AttnParams p) {
 }
 
 template <int D>
-static int launch_ax6(const AttnParams& p, int B, hipStream_t s) {
+static int launch_ax6_ref(const AttnParams& p, int B, hipStream_t s) {
+    dim3 grid(aed_cdiv(p.Nq, 128), p.H, B);
+    hipLaunchKernelGGL((attention_x6_ref_kernel<D>), grid, dim3(256), 0, s, p);
+    AED_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+template <int D>
+static int launch_ax6(const AttnParams& p, int B, bool reference, hipStream_t s) {
+    // buffer loads address bytes below 2 GB of one (batch, head)'s keys, the three dead prefetch tiles included
+    const bool fits = ((long)p.Nk + 96) * (p.ldk > p.ldv ? p.ldk : p.ldv) * 4 < (1L << 31);
+    if (reference || !fits) return launch_ax6_ref<D>(p, B, s);
     dim3 grid(aed_cdiv(p.Nq, 128), p.H, B);
     hipLaunchKernelGGL((attention_x6_kernel<D>), grid, dim3(256), 0, s, p);
     AED_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_attention_x6(const AttnParams& p, int B, int D, hipStream_t s) {
+int launch_attention_x6(const AttnParams& p, int B, int D, bool reference, hipStream_t s) {
     if (((uintptr_t)p.q | (uintptr_t)p.k) % 16 != 0) return -1;          // float4 fragment loads
     switch (D) {
-        case 32: return launch_ax6<32>(p, B, s);
-        case 48: return launch_ax6<48>(p, B, s);
-        case 64: return launch_ax6<64>(p, B, s);
+        case 32: return launch_ax6<32>(p, B, reference, s);
+        case 48: return launch_ax6<48>(p, B, reference, s);
+        case 64: return launch_ax6<64>(p, B, reference, s);
         default: return -1;
     }
 }

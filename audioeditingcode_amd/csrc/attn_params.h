@@ -10,5 +10,7 @@ struct AttnParams {
     float scale;
 };
 
-// attention_x6.hip: the transposed-score kernel on split-bf16 MFMAs.  Returns -1 when it does not take the head dim.
-int launch_attention_x6(const AttnParams& p, int B, int D, hipStream_t s);
+// attention_x6.hip: the transposed-score kernel on split-bf16 MFMAs.  Returns -1 when it does not take the head dim or the
+// operands.  reference: run the kernel body as it was before the vector-instruction diet (same bits; the bit-comparison
+// tests and the A/B tool ask for it through variant 4 of the attention record, the engines never do).
+int launch_attention_x6(const AttnParams& p, int B, int D, bool reference, hipStream_t s);

@@ -410,7 +410,8 @@ class Tape:
     # ------------------------------------------------------------------ attention & friends
     def attention(self, q, k, v, out, *, B, H, Nq, Nk, D, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, scale,
                   bias=None, ld_bias=0, variant=None, name="attn"):
-        """variant: 0 auto (transposed-score kernel when Nk > 64), 1 single-pass kernel, 3 split-bf16 kernel (tests)."""
+        """variant: 0 auto (transposed-score kernel when Nk > 64), 1 single-pass kernel, 3 split-bf16 kernel (tests), 4 that
+        kernel's reference body (bit-comparison tests and tools/attn_x6_diet_ab.py only)."""
         variant = ATTN_VARIANT if variant is None else variant
         # under arith_mode("bf16x6") the record carries flag bit 2: the launcher then takes the split-bf16 kernel
         # (attention_x6.hip) in the throughput regime for the head dims it has (32 / 48 / 64), the fp32 kernels otherwise
