@@ -20,12 +20,12 @@ OP_NOP, OP_CONV_GEMM, OP_GN_STATS, OP_GN_APPLY, OP_LAYERNORM, OP_ATTENTION, OP_G
     OP_TIME_EMBED, OP_SOFTMAX_ROWS, OP_TRANSPOSE, OP_AXPBY, OP_INVERT_STEP, OP_REVERSE_STEP, OP_DDIM_STEP, \
     OP_ADVANCE, OP_REFLECT_PAD, OP_MAGNITUDE, OP_NCHW_TO_NHWC, OP_NHWC_TO_NCHW, OP_SPLITK_REDUCE, \
     OP_GN_SCALE_SHIFT, OP_GN_SMALL, OP_XATTN_FOLD, OP_ROTARY, OP_SNAKE, OP_SA_STEP, OP_GAUSS_SAMPLE, \
-    OP_REVERSE_STEP_VARIANTS, OP_DRIFT_STEP_VARIANTS = range(30)
+    OP_REVERSE_STEP_VARIANTS, OP_DRIFT_STEP_VARIANTS, OP_REVERSE_STEP_ROWS = range(31)
 OP_NAMES = ["nop", "conv_gemm", "gn_stats", "gn_apply", "layernorm", "attention", "geglu", "copy2d", "time_embed",
             "softmax_rows", "transpose", "axpby", "invert_step", "reverse_step", "ddim_step", "advance",
             "reflect_pad", "magnitude", "nchw_to_nhwc", "nhwc_to_nchw", "splitk_reduce", "gn_scale_shift", "gn_small",
             "xattn_fold", "rotary", "snake", "sa_step", "gauss_sample", "reverse_step_variants",
-            "drift_step_variants"]
+            "drift_step_variants", "reverse_step_rows"]
 ACT_NONE, ACT_SILU, ACT_LEAKY, ACT_TANH, ACT_LOGCLAMP = range(5)
 COEF_STRIDE = 8
 SA_COEF_STRIDE = 12
@@ -76,6 +76,7 @@ def lib():
         L.aed_reverse_step_with_custom_noise.argtypes = [vp, vp, vp, vp, cf, ci, fp, ci, vp, vp, ctypes.c_int64, vp]
         L.aed_reverse_step_variants.argtypes = [vp, vp, vp, ci, fp, ci, vp, vp, ctypes.c_int64, vp]
         L.aed_reverse_step_clips.argtypes = [vp, vp, vp, ci, fp, ci, vp, vp, ctypes.c_int64, vp]
+        L.aed_reverse_step_rows.argtypes = [vp, vp, vp, ci, fp, ci, ctypes.POINTER(vp), vp, ctypes.c_int64, vp]
         L.aed_drift_step_variants.argtypes = [vp, vp, vp, ci, fp, ci, vp, vp, vp, ci, ci, vp, vp, ci, cf, ctypes.c_int64, vp]
         L.aed_sample_xts_from_x0.argtypes = [vp, vp, vp, vp, vp, ci, ctypes.c_int64, vp]
         L.aed_mx_quantize_rows.argtypes = [vp, vp, vp, ctypes.c_longlong, ci, vp]
@@ -85,7 +86,7 @@ def lib():
                      "aed_graph_launch", "aed_graph_destroy", "aed_stream_create_cu_mask", "aed_stream_destroy",
                      "aed_cu_census", "aed_image_load", "aed_image_free", "aed_image_run", "aed_image_program",
                      "aed_image_buffer", "aed_image_copy_in", "aed_image_copy_out", "aed_event_create", "aed_event_record", "aed_event_elapsed_ms", "aed_event_destroy", "aed_get_zs_from_xts",
-                     "aed_reverse_step_with_custom_noise", "aed_reverse_step_variants", "aed_reverse_step_clips", "aed_drift_step_variants", "aed_sample_xts_from_x0", "aed_device_info",
+                     "aed_reverse_step_with_custom_noise", "aed_reverse_step_variants", "aed_reverse_step_clips", "aed_reverse_step_rows", "aed_drift_step_variants", "aed_sample_xts_from_x0", "aed_device_info",
                      "aed_sa_get_zs_from_xts", "aed_sa_reverse_step_with_custom_noise", "aed_mx_quantize_rows"):
             getattr(L, name).restype = ci
         if L.aed_version() != 4:
@@ -99,7 +100,7 @@ EXPORTS = ["aed_version", "aed_last_error", "aed_device_info", "aed_launch", "ae
            "aed_stream_destroy", "aed_cu_census", "aed_image_load", "aed_image_free", "aed_image_run", "aed_image_program",
            "aed_image_buffer", "aed_image_copy_in", "aed_image_copy_out", "aed_event_create",
            "aed_event_record", "aed_event_elapsed_ms", "aed_event_destroy", "aed_get_zs_from_xts",
-           "aed_reverse_step_with_custom_noise", "aed_reverse_step_variants", "aed_reverse_step_clips", "aed_drift_step_variants", "aed_sample_xts_from_x0",
+           "aed_reverse_step_with_custom_noise", "aed_reverse_step_variants", "aed_reverse_step_clips", "aed_reverse_step_rows", "aed_drift_step_variants", "aed_sample_xts_from_x0",
            "aed_sa_get_zs_from_xts",
            "aed_sa_reverse_step_with_custom_noise", "aed_mx_quantize_rows"]
 

@@ -397,6 +397,97 @@ int launch_reverse_step_variants(const aed_op* op, hipStream_t s) {
     return launch_clips(ClipStepParams{p, src}, s, "reverse_step_variants");
 }
 
+// ------------------------------------------------------------------------------------ K1 for rows of DIFFERENT methods
+// The same step for `a` rows that differ in where their noise and their coefficients come from (EditEngine.edit_rows: an
+// edit of an inverted clip, an SDEdit run and a DDIM run are rows of one loop).  Two device ints per row: ztab[v] names the
+// noise table the row reads, zs[ztab[v]][Z - s - 1] of zs [N][Z][numel], or is -1 for a row without a noise term, which
+// then reads no z at all (a branch that is uniform across the wave, not a multiply by zero); ctab[v] names the row's
+// coefficient table, coef [R][steps][AED_COEF_STRIDE].  The explicit form (aed_reverse_step_rows) carries one z pointer or
+// null and one host coefficient row per row in the kernel arguments instead.  Everything else is
+// reverse_step_clips_kernel: the same cfg_combine form and the shared reverse_update, so row v is bit-identical to
+// reverse_step_kernel run on that row alone with its own coefficients, cfg and z.  Neither int is range-checked here; the
+// engine validates both on the host (editing.rows_plan).
+#define AED_ROWS_MAX_EXPLICIT 16
+struct RowStepParams {
+    VariantStepParams v;   // zs: [N][Z][numel] or null; coef: [R][steps][AED_COEF_STRIDE] (device form)
+    const int* ztab;       // [a] noise table of every row (device), -1 = no noise term; null => the explicit form
+    const int* ctab;       // [a] coefficient table of every row (device)
+    int steps;             // rows of one coefficient table
+    const float* z_row[AED_ROWS_MAX_EXPLICIT];   // explicit form: one z [numel] or null per row
+    float c_row[AED_ROWS_MAX_EXPLICIT][5];       //                one coefficient row per row
+};
+
+__global__ __launch_bounds__(256) void reverse_step_rows_kernel(RowStepParams q) {
+    const VariantStepParams& p = q.v;
+    const int s = p.state ? p.state[0] * p.s_mul + p.s_off : p.s_imm;
+    const float* eps_c = p.eps + (size_t)p.a * p.numel;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < p.numel; e += (size_t)gridDim.x * 256) {
+        for (int v0 = 0; v0 < p.a; v0 += 4) {                         // 4 rows' loads issued before the first store:
+            float x[4], u[4], c[4], zz[4];                            // out may alias cur, so stores would order them
+            bool nz[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = v0 + j;
+                if (v >= p.a) break;
+                const size_t o = (size_t)v * p.numel + e;
+                x[j] = p.cur[o]; u[j] = p.eps[o]; c[j] = eps_c[o];
+                const float* z = nullptr;
+                if (!q.ztab) z = q.z_row[v];
+                else if (p.zs && q.ztab[v] >= 0) z = p.zs + ((size_t)q.ztab[v] * p.Z + (size_t)(p.Z - s - 1)) * p.numel;
+                nz[j] = z != nullptr;
+                zz[j] = 0.f;
+                if (nz[j]) zz[j] = z[e];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = v0 + j;
+                if (v >= p.a) break;
+                float c0, c1, c2, c3, c4;
+                if (q.ztab) {
+                    const float* cr = p.coef + ((size_t)q.ctab[v] * q.steps + s) * AED_COEF_STRIDE;
+                    c0 = cr[0]; c1 = cr[1]; c2 = cr[2]; c3 = cr[3]; c4 = cr[4];
+                } else { c0 = q.c_row[v][0]; c1 = q.c_row[v][1]; c2 = q.c_row[v][2]; c3 = q.c_row[v][3]; c4 = q.c_row[v][4]; }
+                const float eps = u[j] + p.cfg[v] * (c[j] - u[j]);     // cfg_combine, P = 1
+                const size_t o = (size_t)v * p.numel + e;             // two calls: &zz[j] must not meet null in a select
+                if (nz[j]) p.out[o] = reverse_update(x[j], eps, &zz[j], 0, p.v_pred, c0, c1, c2, c3, c4);
+                else p.out[o] = reverse_update(x[j], eps, nullptr, 0, p.v_pred, c0, c1, c2, c3, c4);
+            }
+        }
+    }
+}
+
+static int launch_rows(const RowStepParams& q, hipStream_t s, const char* what) {
+    if (int rc = check_variants(q.v, what)) return rc;
+    if (q.v.numel == 0) return 0;
+    hipLaunchKernelGGL(reverse_step_rows_kernel, dim3(grid_for(q.v.numel)), dim3(256), 0, s, q);
+    AED_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// slots: p0=cur [K][numel] (rows [0, a) stepped)  p1=zs [N][Z][numel] | null (no row has noise)  p2=eps [2a][numel]
+//        p3=ztab int[a] (device; noise table of a row, -1 = none)  p4=cfg [a] (device)  p5=coef [R][steps][8]
+//        p6=state (nullable)  p7=out (null => in place into p0)  p8=ctab int[a] (device; coefficient table of a row)
+//   i0,i1=numel lo/hi  i2=a  i3=Z (noise maps per table)  i4=s_imm  i5=v_pred  i6=has_noise (some row reads p1)
+//   i7=s_mul i8=s_off (step = state*s_mul + s_off)  i9=N  i10=R  i11=steps (rows per coefficient table)
+int launch_reverse_step_rows(const aed_op* op, hipStream_t s) {
+    RowStepParams q = {};
+    VariantStepParams& p = q.v;
+    p.cur = (const float*)op->p[0];
+    p.zs = op->i[6] ? (const float*)op->p[1] : nullptr;
+    p.eps = (const float*)op->p[2]; p.cfg = (const float*)op->p[4];
+    p.coef = (const float*)op->p[5]; p.state = (const int*)op->p[6];
+    p.out = op->p[7] ? (float*)op->p[7] : (float*)op->p[0];
+    p.numel = (size_t)(uint32_t)op->i[0] | ((size_t)(uint32_t)op->i[1] << 32);
+    p.a = op->i[2]; p.Z = op->i[3]; p.s_imm = op->i[4]; p.v_pred = op->i[5];
+    p.s_mul = op->i[7] > 0 ? op->i[7] : 1; p.s_off = op->i[8];
+    q.ztab = (const int*)op->p[3]; q.ctab = (const int*)op->p[8]; q.steps = op->i[11];
+    AED_REQUIRE(q.ztab && q.ctab && p.coef, "reverse_step_rows: null row table or coefficient table");
+    AED_REQUIRE(!op->i[6] || op->p[1], "reverse_step_rows: noise requested but zs is null");
+    AED_REQUIRE(!p.zs || (op->i[9] >= 1 && p.Z >= 1), "reverse_step_rows: %d noise tables of %d maps", op->i[9], p.Z);
+    AED_REQUIRE(op->i[10] >= 1 && q.steps >= 1, "reverse_step_rows: %d coefficient tables of %d rows", op->i[10], q.steps);
+    return launch_rows(q, s, "reverse_step_rows");
+}
+
 // ------------------------------------------------------------------------------------ K1 for K principal-component drifts
 // One step of `a` rows that replay ONE recorded trajectory (EditEngine.drift_variants): reverse_step_variants_kernel's
 // CFG combine and step with the recorded noise, then -- for a row that has a non-zero weight at this loop step --
@@ -620,6 +711,25 @@ extern "C" int aed_reverse_step_clips(const float* xt, const float* eps, const f
     AED_REQUIRE(coef_host && numel >= 0, "aed_reverse_step_clips: null coefficients or negative numel");
     for (int k = 0; k < 5; ++k) p.c[k] = coef_host[k];
     return launch_clips(ClipStepParams{p, nullptr}, (hipStream_t)stream, "aed_reverse_step_clips");
+}
+
+extern "C" int aed_reverse_step_rows(const float* xt, const float* eps, const float* cfg, int n_rows,
+                                     const float* coef_rows_host, int v_prediction, const float* const* z_rows_host,
+                                     float* prev_out, int64_t numel, void* stream) {
+    RowStepParams q = {};
+    VariantStepParams& p = q.v;
+    p.s_mul = 1;
+    p.cur = xt; p.out = prev_out; p.eps = eps; p.cfg = cfg; p.a = n_rows;
+    p.v_pred = v_prediction; p.numel = (size_t)numel;
+    AED_REQUIRE(coef_rows_host && z_rows_host && numel >= 0,
+                "aed_reverse_step_rows: null coefficients, null list of z rows or negative numel");
+    AED_REQUIRE(n_rows <= AED_ROWS_MAX_EXPLICIT, "aed_reverse_step_rows: %d rows, at most %d", n_rows,
+                AED_ROWS_MAX_EXPLICIT);
+    for (int v = 0; v < n_rows; ++v) {
+        q.z_row[v] = z_rows_host[v];
+        for (int k = 0; k < 5; ++k) q.c_row[v][k] = coef_rows_host[(size_t)v * AED_COEF_STRIDE + k];
+    }
+    return launch_rows(q, (hipStream_t)stream, "aed_reverse_step_rows");
 }
 
 extern "C" int aed_drift_step_variants(float* xt, const float* eps, const float* cfg, int n_rows, const float* coef_host,

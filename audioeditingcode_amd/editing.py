@@ -195,6 +195,60 @@ def clip_join_rows(xts_list, clips, tstarts, order, seg):
     return torch.stack([xts_list[clips[order[i]]][tstarts[order[i]], 0] for i in range(lo, hi)])
 
 
+ROW_STEPS = ("ddpm", "ddim")     # the step of a row of EditEngine.edit_rows: reverse_step_with_custom_noise / scheduler.step(eta=0)
+ROW_KINDS = ("audioldm", "audioldm2", "tango")
+
+
+def rows_plan(tables, rows, T, kind, latent_shape=None, max_rows=None):
+    """The host plan of EditEngine.edit_rows.  tables: the noise tables [Z_i, 1, H, W, C]; rows: (x_start, tstart, table
+    index or None, "ddpm" | "ddim", ...); T: the schedule's steps; kind: the engine's.  Returns dict(tstarts, order, segs:
+    variant_plan's over the rows' tstarts; ztab: per row the table it reads or -1; ctab: per row its coefficient table;
+    coefs: the table kinds, "ddpm" first and "ddim_prev" behind it when a row asks for it).  Refuses an empty list, more
+    than `max_rows`, a tstart outside [1, T] or beyond the row's table, a table index outside the list, a "ddim" row
+    with a table, a table or (with `latent_shape` = (H, W, C)) an x_start of another shape, and an engine kind other than
+    AudioLDM / AudioLDM2 / TANGO."""
+    if kind not in ROW_KINDS:
+        raise ValueError(f"edit_rows: engine kind {kind!r} is not supported (AudioLDM, AudioLDM2, TANGO)")
+    rows, tables = list(rows), list(tables)
+    if not rows:
+        raise ValueError("edit_rows: the list of rows is empty")
+    if max_rows is not None and len(rows) > max_rows:
+        raise ValueError(f"edit_rows: {len(rows)} rows in one call, at most {max_rows} (grid.run_grid splits longer lists)")
+    want = None if latent_shape is None else (1, *latent_shape)
+    for i, z in enumerate(tables):
+        if want is not None and (z.dim() != 5 or tuple(z.shape[1:]) != want):
+            raise ValueError(f"edit_rows: noise table {i} is {tuple(z.shape)}, expected [Z, 1, H, W, C] = {['Z', *want]}")
+    tstarts, ztab, ctab = [], [], []
+    for k, row in enumerate(rows):
+        t, tab, step = int(row[1]), row[2], row[3]
+        if step not in ROW_STEPS:
+            raise ValueError(f"edit_rows: row {k} has step {step!r}, expected one of {list(ROW_STEPS)}")
+        if not 1 <= t <= T:
+            raise ValueError(f"edit_rows: row {k} has tstart {t} outside [1, {T}] (the steps of the schedule)")
+        if tab is not None:
+            if step == "ddim":
+                raise ValueError(f"edit_rows: row {k} is a \"ddim\" row with a noise table (the DDIM step adds no noise)")
+            tab = int(tab)
+            if not 0 <= tab < len(tables):
+                raise ValueError(f"edit_rows: row {k} names noise table {tab}, outside [0, {len(tables)})")
+            if t > tables[tab].shape[0]:
+                raise ValueError(f"edit_rows: row {k} has tstart {t} outside [1, {tables[tab].shape[0]}] (the number of "
+                                 f"noise maps table {tab} holds)")
+        if want is not None and tuple(row[0].shape) != want:
+            raise ValueError(f"edit_rows: row {k} starts from {tuple(row[0].shape)}, expected [1, H, W, C] = {list(want)}")
+        tstarts.append(t)
+        ztab.append(-1 if tab is None else tab)
+        ctab.append(ROW_STEPS.index(step))
+    coefs = ["ddpm"] + (["ddim_prev"] if any(ctab) else [])
+    order, segs = variant_plan(tstarts, T, max_rows)
+    return dict(tstarts=tstarts, order=order, segs=segs, ztab=ztab, ctab=ctab, coefs=coefs)
+
+
+def row_noise_fill(buf, tables):
+    """clip_noise_fill for tables [Z_i, 1, H, W, C]; a buffer without tables (no row has noise) is left alone."""
+    return clip_noise_fill(buf, tables) if tables else buf
+
+
 MAX_DRIFT_EV = 8         # PCs per timestep the drift step kernel takes (AED_DRIFT_MAX_EV in csrc/elementwise.hip)
 
 
@@ -742,7 +796,7 @@ class EditEngine(LoopPlumbing):
     MAX_VARIANTS = 16       # rows per edit_variants / edit_clips call (U-Net batch <= 32); variants.py and batch.py chunk
 
     def _variant_loop(self, tag, order, segs, tgt, neg, cfgs, eta, noise_ok, fill_noise, join_rows, use_graph, src=None,
-                      n_tables=0, drift=None, n_steps=None):
+                      n_tables=0, drift=None, n_steps=None, rowsel=None):
         """The segmented loop of edit_variants and edit_clips.  order / segs: variant_plan's; tgt / neg / cfgs: per row in
         the caller's order; fill_noise(buf) loads the plan's noise buffer, join_rows(seg) returns the x_t rows that start
         at a segment from (segment, the loop's row buffer).  src (the table of every row, caller's order) with n_tables makes
@@ -761,19 +815,26 @@ class EditEngine(LoopPlumbing):
         groups_all = [neg[v] for v in order] + [tgt[v] for v in order]
         L0, L1 = self._ctx_lens(groups_all)
         tables = () if src is None else (n_tables,)
+        R = None if rowsel is None else len(rowsel["coefs"])
+        rkey = () if rowsel is None else (n_tables, R)
+        if rowsel is not None:
+            tables = (max(n_tables, 1),)
         dkey = () if drift is None else (tuple(drift["vecs"].shape[:2]), drift["s_first"], bool(drift["shift_np"]),
                                           drift["fix_mode"], float(drift["fix_alpha"]))
-        key = (tag, K, *tables, T, tuple(sg["tstart"] for sg in segs), tuple(sg["a"] for sg in segs), L0, L1, v_pred,
-               has_noise, tuple(self._arith_for(2 * sg["a"]) for sg in segs), *dkey)
+        key = (tag, K, *(tables if rowsel is None else ()), T, tuple(sg["tstart"] for sg in segs),
+               tuple(sg["a"] for sg in segs), L0, L1, v_pred, has_noise,
+               tuple(self._arith_for(2 * sg["a"]) for sg in segs), *dkey, *rkey)
         plan = self._get_plan(key)
         if plan is None:
             plan = self._plans[key] = dict(
                 state=torch.zeros(4, dtype=torch.int32, device=self.device),
                 cur=torch.empty((K, self.H, self.W, self.C), device=self.device, dtype=torch.float32),
                 zs=torch.zeros((*tables, Z0, self.H, self.W, self.C), device=self.device, dtype=torch.float32),
-                coef=torch.zeros((Z0, L.COEF_STRIDE), device=self.device, dtype=torch.float32),
+                coef=torch.zeros((*(() if R is None else (R,)), Z0, L.COEF_STRIDE), device=self.device, dtype=torch.float32),
                 cfg=torch.zeros(K, device=self.device, dtype=torch.float32),
                 src=None if src is None else torch.zeros(K, device=self.device, dtype=torch.int32), segs=[])
+            if rowsel is not None:      # one int pair per row: [0] the noise table (-1: none), [1] the coefficient table
+                plan["rowsel"] = torch.zeros((2, K), device=self.device, dtype=torch.int32)
             if drift is not None:
                 S, n_ev = drift["vecs"].shape[:2]
                 dev_buf = lambda *shape: torch.zeros(shape, device=self.device, dtype=torch.float32)      # noqa: E731
@@ -789,7 +850,9 @@ class EditEngine(LoopPlumbing):
                                ld_dst=a * numel, name="x_in<-x_t")
                 step = dict(cur=plan["cur"], zs=plan["zs"] if has_noise else None, eps=eng.eps[:2 * a], cfg=plan["cfg"],
                             coef=plan["coef"], state=plan["state"], numel=numel, a=a, Z=Z0, v_pred=v_pred)
-                if drift is None:
+                if rowsel is not None:
+                    post.step_rows(**step, ztab=plan["rowsel"][0], ctab=plan["rowsel"][1], N=tables[0], R=R, steps=Z0)
+                elif drift is None:
                     post.step_variants(**step, src=plan["src"], N=n_tables)
                 else:       # the stored trajectory's x_{t-1} of loop step s is its point s + 1 (main_pc_apply_drift.py:153)
                     post.drift_step_variants(**step, vecs=plan["vecs"], w=plan["w"], n_ev=n_ev, a_max=K,
@@ -803,7 +866,14 @@ class EditEngine(LoopPlumbing):
         cur = plan["cur"]
         if has_noise:
             fill_noise(plan["zs"])
-        plan["coef"].copy_(self._coef_table(s, s.timesteps.cpu()[T - Z0:], eta_rows, "ddpm"))
+        ts_loop = s.timesteps.cpu()[T - Z0:]
+        if rowsel is None:
+            plan["coef"].copy_(self._coef_table(s, ts_loop, eta_rows, "ddpm"))
+        else:       # refilled on every call (the captured graphs hold the buffers, not their contents)
+            plan["coef"].copy_(torch.stack([self._coef_table(s, ts_loop, eta_rows if k == "ddpm" else 0.0, k)
+                                            for k in rowsel["coefs"]]))
+            plan["rowsel"].copy_(torch.tensor([[rowsel["ztab"][v] if has_noise else -1 for v in order],
+                                               [rowsel["ctab"][v] for v in order]], dtype=torch.int32))
         plan["cfg"].copy_(torch.tensor([float(cfgs[v]) for v in order], dtype=torch.float32))
         if src is not None:
             plan["src"].copy_(torch.tensor([src[v] for v in order], dtype=torch.int32))
@@ -890,6 +960,37 @@ class EditEngine(LoopPlumbing):
             fill_noise=lambda buf: clip_noise_fill(buf, zs_list),
             join_rows=lambda sg, cur: clip_join_rows(xts_list, clips, tstarts, order, sg),
             use_graph=use_graph, src=clips, n_tables=len(xts_list))     # clips: validated in clip_plan, all < N
+
+    # ------------------------------------------------------------------ rows of different methods
+    @torch.inference_mode()
+    def edit_rows(self, tables, rows, eta=1.0, use_graph=True):
+        """K runs of DIFFERENT methods in one device-resident loop: an edit of an inverted clip, an SDEdit run and a DDIM
+        sampling run differ only in where a row starts, which noise it adds and which coefficients its step uses.
+        tables: a list of noise tables [Z_i, 1, H, W, C] (channels-last; an inversion's recorded zs, or SDEdit's fresh
+        draws).  rows: a list of (x_start [1, H, W, C], tstart, table index or None, "ddpm" | "ddim", cond_tgt, cond_neg,
+        cfg) with one-row Conditioning objects.  Row k is that method's single run from x_start at loop position
+        T - tstart: "ddpm" with table i is `edit(xts, tables[i], tstart, cond_tgt, cond_neg, [cfg], eta)` with
+        xts[tstart] = x_start, "ddim" (no table) is `ddim_sample(x_start, cond_tgt, cond_neg, cfg, skip=T - tstart)`.
+        eta: as in edit_clips, for the "ddpm" rows.
+
+        The loop is edit_clips' (rows sorted by tstart, largest first; segments between the distinct tstarts at U-Net
+        batch 2a; the same engines, tapes and graphs per segment) with the rows step (AED_OP_REVERSE_STEP_ROWS): per row
+        a noise table or none and a coefficient table, "ddpm" (from eta) or "ddim_prev".
+        Returns the latents [K, H, W, C] in the caller's order."""
+        rows = list(rows)
+        plan = rows_plan(tables, rows, self.sched.num_inference_steps, self.kind, (self.H, self.W, self.C),
+                         self.MAX_VARIANTS)
+        K, order, tables = len(rows), plan["order"], list(tables)
+        tgt = _variant_rows([r[4] for r in rows], K, "cond_tgt")
+        neg = _variant_rows([r[5] for r in rows], K, "cond_neg")
+
+        def join(sg, cur):
+            lo, hi = sg["join"]
+            return torch.stack([rows[order[i]][0][0].to(self.device, torch.float32) for i in range(lo, hi)])
+        return self._variant_loop(
+            "rows", order, plan["segs"], tgt, neg, [r[6] for r in rows], eta, any(z >= 0 for z in plan["ztab"]),
+            fill_noise=lambda buf: row_noise_fill(buf, tables), join_rows=join, use_graph=use_graph,
+            n_tables=len(tables), rowsel=plan)
 
     # ------------------------------------------------------------------ K principal-component drifts of one trajectory
     MAX_DRIFT_VARIANTS = 15     # variants per drift_variants call; with the trunk row the U-Net batch stays <= 32
@@ -994,6 +1095,73 @@ class EditEngine(LoopPlumbing):
             post.run()
         self._run_graph(body, steps, use_graph)
         return cur
+
+    @torch.inference_mode()
+    def ddim_invert_rows(self, w0, cond_src, cond_uncond, cfg_srcs, depths, use_graph=True):
+        """ddim_invert for n rows in one loop, each with its own source prompt and guidance, read out at several depths.
+        w0 [n, C, H, W]; cond_src: n one-row Conditioning objects (or one Conditioning with n rows, or 1 shared row);
+        cond_uncond: one row; cfg_srcs: n guidance scales; depths: the tstarts wanted, each in [1, T].  Row r at depth d
+        is `ddim_invert(w0[r:r + 1], cond_src[r], cond_uncond, cfg_srcs[r], skip=T - d)`.  Returns {d: [n, H, W, C]}.
+
+        The loop runs to the deepest depth in segments between the distinct depths (one plan, one graph, the device step
+        counter continues across segments) and copies EVERY row out at each requested depth; a row keeps stepping past a
+        depth it no longer needs (no early exit: all n rows are U-Net batch rows up to the deepest depth).  The step is
+        the variants step op with the `ddim_next` table and no noise term: the same reverse_update form ddim_invert runs
+        through OP_REVERSE_STEP, with the model output taken as eps as there."""
+        if self.kind not in ("audioldm", "audioldm2", "tango"):
+            raise ValueError(f"ddim_invert_rows: engine kind {self.kind!r} is not supported (AudioLDM, AudioLDM2, TANGO)")
+        s = self.sched
+        T = s.num_inference_steps
+        n = w0.shape[0]
+        if not 1 <= n <= self.MAX_VARIANTS:
+            raise ValueError(f"ddim_invert_rows: {n} rows in one call, between 1 and {self.MAX_VARIANTS}")
+        if len(cfg_srcs) != n:
+            raise ValueError(f"ddim_invert_rows: {len(cfg_srcs)} cfg_src values for {n} rows")
+        depths = sorted({int(d) for d in depths})
+        if not depths or depths[0] < 1 or depths[-1] > T:
+            raise ValueError(f"ddim_invert_rows: depths {depths} must be a non-empty set inside [1, {T}]")
+        numel = self.C * self.H * self.W
+        groups = _variant_rows(cond_uncond, 1, "cond_uncond") * n + _variant_rows(cond_src, n, "cond_src")
+        L0, L1 = self._ctx_lens(groups)
+        key = ("ddim_invert_rows", n, T, L0, L1, self._arith_for(2 * n))
+        plan = self._get_plan(key)
+        if plan is None:
+            plan = self._plans[key] = dict(
+                state=torch.zeros(4, dtype=torch.int32, device=self.device),
+                cur=torch.empty((n, self.H, self.W, self.C), device=self.device, dtype=torch.float32),
+                coef=torch.zeros((T, L.COEF_STRIDE), device=self.device, dtype=torch.float32),
+                cfg=torch.zeros(n, device=self.device, dtype=torch.float32))
+            eng = plan["eng"] = self.unet(2 * n, L0, L1)
+            pre, post = Tape(self.device), Tape(self.device)
+            for blk in range(2):
+                pre.copy2d(plan["cur"], eng.x_in[blk * n:(blk + 1) * n], rows=1, cols=n * numel, ld_src=n * numel,
+                           ld_dst=n * numel, name="x_in<-x_t")
+            post.step_variants(cur=plan["cur"], zs=None, eps=eng.eps[:2 * n], cfg=plan["cfg"], coef=plan["coef"],
+                               state=plan["state"], numel=numel, a=n, Z=0)
+            post.advance(plan["state"])
+            pre.finalize()
+            post.finalize()
+            plan["pre"], plan["post"] = pre, post
+        eng, pre, post, cur = plan["eng"], plan["pre"], plan["post"], plan["cur"]
+        ts_asc = torch.flip(s.timesteps.cpu(), dims=[0])
+        plan["coef"].copy_(self._coef_table(s, ts_asc, 0.0, "ddim_next"))
+        plan["cfg"].copy_(torch.tensor([float(c) for c in cfg_srcs], dtype=torch.float32))
+        self.ts_dev[:T] = ts_asc.to(self.device)
+        self._ts_host = None                            # the table no longer holds the descending schedule
+        self._set_cond(eng, groups)
+        self._patch_time(eng, self.ts_dev, 1, 2 * n, state=plan["state"])
+        self.to_nhwc(w0, out=cur)
+        plan["state"].zero_()
+
+        def body():
+            pre.run()
+            eng.tape.run()
+            post.run()
+        out, done = {}, 0
+        for d in depths:
+            self._run_graph(body, d - done, use_graph, plan)
+            out[d], done = cur.clone(), d
+        return out
 
     @torch.inference_mode()
     def ddim_sample(self, xt, cond_tgt, cond_uncond, guidance_scale, skip=0, use_graph=True):

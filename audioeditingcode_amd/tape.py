@@ -515,6 +515,17 @@ class Tape:
                   [0.0, *c_imm], [cur, zs, eps, src, cfg, coef, state, out], name=name,
                   nbytes=4 * numel * (4 * a + has_noise * (1 if src is None else a)))
 
+    def step_rows(self, *, cur, zs, eps, cfg, coef, state, numel, a, Z, ztab, ctab, N, R, steps, v_pred=0, out=None,
+                  s_imm=0, s_mul=1, s_off=0, name="step_rows"):
+        """step_variants for `a` rows of different methods (AED_OP_REVERSE_STEP_ROWS): ztab (a device int32[>= a]) names
+        the table of zs [N, Z, numel] a row reads, -1 for a row without a noise term (zs=None: no row has one); ctab
+        (int32[>= a]) names its table of coef [R, steps, COEF_STRIDE] (EditEngine.edit_rows)."""
+        has_noise = int(zs is not None)
+        self._add(L.OP_REVERSE_STEP_ROWS, [numel & 0xFFFFFFFF, numel >> 32, a, Z, s_imm, v_pred, has_noise, s_mul, s_off,
+                                           N, R, steps],
+                  [], [cur, zs, eps, ztab, cfg, coef, state, out, ctab], name=name,
+                  nbytes=4 * numel * (4 * a + has_noise * a))
+
     def drift_step_variants(self, *, cur, zs, eps, cfg, coef, state, numel, a, Z, vecs, w, n_ev, a_max, s_first, S,
                             v_pred=0, shift_np=True, mask=None, par=None, fix_mode=0, par_off=0, fix_alpha=0.0, s_imm=0,
                             c_imm=(0, 0, 0, 0, 0), s_mul=1, s_off=0, name="drift_step_variants"):

@@ -103,6 +103,11 @@ enum aed_opcode {
                                  vecs[step][e] and the optional fix_alpha blend towards the undrifted parallel trajectory (a
                                  table indexed by loop step, or row 0 of the launch), in place.  A row whose weights are all
                                  zero is bit-identical to opcode 28 (EditEngine.drift_variants)                             */
+    AED_OP_REVERSE_STEP_ROWS = 30, /* opcode 28's step for `a` rows of DIFFERENT methods: two device int[a] name, per row, the
+                                 noise table it reads (zs [N][Z][numel], row Z - step - 1; -1: no noise term and no z read)
+                                 and its coefficient table (coef [R][steps][AED_COEF_STRIDE]).  Row v is bit-identical to
+                                 AED_OP_REVERSE_STEP with P = 1, cfg_scalar = cfg[v], its own table row and its own z or none
+                                 (EditEngine.edit_rows: edits, SDEdit and DDIM runs as rows of one loop)                   */
     AED_OP_COUNT
 };
 
@@ -213,6 +218,14 @@ int aed_reverse_step_variants(const float* xt, const float* eps, const float* cf
  * (xt[v], {eps[v], eps[n_rows + v]}, cfg[v], 1 variant, z[v]).                                                          */
 int aed_reverse_step_clips(const float* xt, const float* eps, const float* cfg, int n_rows, const float* coef_host,
                            int v_prediction, const float* z, float* prev_out, int64_t numel, void* stream);
+
+/* aed_reverse_step_clips for n_rows (at most 16) rows that differ in their step: coef_rows_host holds one coefficient row
+ * per row, [n_rows][AED_COEF_STRIDE], and z_rows_host is a HOST array of n_rows device pointers, one z [numel] per row or
+ * NULL for a row without a noise term (no z is read for it).  Row v is bit-identical to
+ * aed_reverse_step_with_custom_noise(xt[v], eps[v], eps[n_rows + v], NULL, cfg[v], 1, coef_rows_host + v * AED_COEF_STRIDE,
+ * v_prediction, z_rows_host[v], prev_out[v], numel, stream).                                                             */
+int aed_reverse_step_rows(const float* xt, const float* eps, const float* cfg, int n_rows, const float* coef_rows_host,
+                          int v_prediction, const float* const* z_rows_host, float* prev_out, int64_t numel, void* stream);
 
 /* aed_reverse_step_variants followed by the principal-component drift of pc_drift.py:201-278, one launch, IN PLACE on
  * xt [n_rows][numel]: eps, cfg, coef_host, z as above; vecs [n_ev][numel] are the PC directions of this timestep and
