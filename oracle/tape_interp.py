@@ -291,17 +291,21 @@ def _step_common(op):
     s_mul, s_off = (int(i[7]) if int(i[7]) > 0 else 1), int(i[8])
     s = _state0(p[6]) * s_mul + s_off if p[6] else s_imm
     c = _f32(int(p[5]) + 4 * 8 * s, 8) if p[5] else torch.tensor([float(f[1 + k]) for k in range(5)])
-    eps_u = _f32(p[2], numel)
-    eps = eps_u
-    if p[3]:
-        eps_c = _f32(p[3], P * numel).reshape(P, numel)
-        acc = None
-        for j in range(P):
-            g = _f32(p[4], P * numel).reshape(P, numel)[j] if p[4] else float(f[0])
-            term = g * (eps_c[j] - eps_u)
-            acc = term if acc is None else acc + term
-        eps = eps_u + acc
-    return numel, T, s, v_pred, flag, c, eps
+    return numel, T, s, v_pred, flag, c, _cfg_combine(p[2], p[3], p[4], float(f[0]), P, numel)
+
+
+def _cfg_combine(eps_u, eps_c, cfg, cfg_scalar, P, numel):
+    """eps_u + sum_j g_j * (eps_c[j] - eps_u) over the P conditional passes (g: per-element tensor [P, numel] or a scalar)."""
+    eps_u = _f32(eps_u, numel)
+    if not eps_c:
+        return eps_u
+    eps_c = _f32(eps_c, P * numel).reshape(P, numel)
+    acc = None
+    for j in range(P):
+        g = _f32(cfg, P * numel).reshape(P, numel)[j] if cfg else torch.tensor(cfg_scalar, dtype=torch.float32)
+        term = g * (eps_c[j] - eps_u)
+        acc = term if acc is None else acc + term
+    return eps_u + acc
 
 
 def _x0_dir(x, eps, c, v_pred):
@@ -497,20 +501,22 @@ class FakeLib:
     def aed_get_zs_from_xts(self, xt, xtm1, eps_u, eps_c, cfg, cfg_scalar, n_prompts, coef_host, v_pred, fix, z,
                             noise_pred_out, numel, stream):
         c = torch.tensor([float(coef_host[k]) for k in range(5)])
-        x, xm1, eps = _f32(xt, numel), _f32(xtm1, numel), _f32(eps_u, numel)
-        assert not eps_c, "the wrapper passes the combined prediction"
+        x, xm1 = _f32(xt, numel), _f32(xtm1, numel)
+        eps = _cfg_combine(eps_u, eps_c, cfg, float(cfg_scalar), n_prompts, numel)
         x0, d = _x0_dir(x, eps, c, v_pred)
         mu = c[2] * x0 + c[3] * d
         zz = (xm1 - mu) / c[4]
         _f32(z, numel).copy_(zz)
         if fix:
             xm1.copy_(mu + c[4] * zz)
+        if noise_pred_out:
+            _f32(noise_pred_out, numel).copy_(eps)
         return 0
 
     def aed_reverse_step_with_custom_noise(self, xt, eps_u, eps_c, cfg, cfg_scalar, n_prompts, coef_host, v_pred, z,
                                            prev_out, numel, stream):
         c = torch.tensor([float(coef_host[k]) for k in range(5)])
-        x0, d = _x0_dir(_f32(xt, numel), _f32(eps_u, numel), c, v_pred)
+        x0, d = _x0_dir(_f32(xt, numel), _cfg_combine(eps_u, eps_c, cfg, float(cfg_scalar), n_prompts, numel), c, v_pred)
         prev = c[2] * x0 + c[3] * d
         if z:
             prev = prev + c[4] * _f32(z, numel)
