@@ -26,6 +26,10 @@ OP_NAMES = ["nop", "conv_gemm", "gn_stats", "gn_apply", "layernorm", "attention"
             "reflect_pad", "magnitude", "nchw_to_nhwc", "nhwc_to_nchw", "splitk_reduce", "gn_scale_shift", "gn_small",
             "xattn_fold", "rotary", "snake", "sa_step", "gauss_sample", "reverse_step_variants",
             "drift_step_variants", "reverse_step_rows"]
+# the power iteration of the PC extraction (csrc/pc.hip); tape.py's helpers name these records themselves
+OP_PC_PROBE, OP_PC_JACOBIAN, OP_PC_ORTHONORMALISE = 31, 32, 33
+PC_TAB_STRIDE = 4           # floats per slot of the ops' table: sqrt(abar_t), c0, c1, sigma_t^2 / const
+PC_MAX_EV = 8               # directions AED_OP_PC_ORTHONORMALISE takes
 ACT_NONE, ACT_SILU, ACT_LEAKY, ACT_TANH, ACT_LOGCLAMP = range(5)
 COEF_STRIDE = 8
 SA_COEF_STRIDE = 12

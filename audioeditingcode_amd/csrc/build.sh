@@ -15,6 +15,7 @@ hipcc $FLAGS -c attention_x6.hip -o obj/attention_x6.o & pids+=($!)
 hipcc $FLAGS -c norm.hip -o obj/norm.o & pids+=($!)
 hipcc $FLAGS -ffp-contract=off -c elementwise.hip -o obj/elementwise.o & pids+=($!)
 hipcc $FLAGS -ffp-contract=off -c stable_audio.hip -o obj/stable_audio.o & pids+=($!)
+hipcc $FLAGS -ffp-contract=off -c pc.hip -o obj/pc.o & pids+=($!)
 hipcc $FLAGS -c api.hip -o obj/api.o & pids+=($!)
 hipcc $FLAGS -c image.hip -o obj/image.o & pids+=($!)
 for p in "${pids[@]}"; do wait $p; done

@@ -24,7 +24,7 @@ import math
 import torch
 
 from . import _lib as L
-from .scheduler import coefficient_table
+from .scheduler import coefficient_table, step_coefficients
 from . import tape as tape_mod
 from .tape import Tape
 from .unet import PackedUNetWeights, UNetEngine
@@ -1058,6 +1058,112 @@ class EditEngine(LoopPlumbing):
             fill_noise=lambda buf: buf.copy_(zs.reshape(T, *lat)), join_rows=join, use_graph=use_graph, drift=drift,
             n_steps=n_steps)
         return out[1:]
+
+    # ------------------------------------------------------------------ PC extraction: a group of timesteps per iteration
+    MAX_PC_ROWS = 256       # U-Net rows (2 * n_ev * timesteps) of one pc_window call
+
+    @torch.inference_mode()
+    def pc_window(self, xts, x0_preds, mask, ts, cond_text, cond_uncond, init, to_eigval, *, pc_mode=1, const=1e-3,
+                  cfg_tar=3.0, iters=50, eta=1.0, use_graph=True):
+        """pc_drift.get_eigenvectors for the G timesteps `ts` at once: every power iteration is ONE U-Net call of batch
+        2 * k * G (rows [g][uncond x k | text x k]) between the probe kernel and the Jacobian / orthonormalise kernels, and the
+        `iters` iterations replay one captured graph; the host reads nothing inside the loop.  xts, x0_preds [G, C, H, W]
+        (x_t and the undrifted, masked-or-not x0_hat the per-timestep call is given), mask [C, H, W], init [G, k, C, H, W]
+        the start vectors, to_eigval [G] = sigma_t^2 / const, cond_text / cond_uncond one-row Conditioning; pc_mode 1 both
+        streams, 2 text, 3 uncond.  Returns a dict of device tensors: unit and probe [G, k, C, H, W] of the last iteration,
+        in_norm [iters, G, k] (unsorted lengths), in_corr [iters - 1, G, k], snap_vec [S, G, k, C, H, W] and snap_val
+        [S, G, k] for the iterations 20, 30, ... below iters."""
+        if self.kind not in ("audioldm", "audioldm2", "tango"):
+            raise ValueError(f"pc_window: engine kind {self.kind!r} is not supported (AudioLDM, AudioLDM2, TANGO)")
+        s = self.sched
+        lat = (self.C, self.H, self.W)
+        N = math.prod(lat)
+        ts = [int(t) for t in ts]
+        G = len(ts)
+        iters = int(iters)
+        if G < 1 or iters < 1:
+            raise ValueError(f"pc_window: {G} timesteps and {iters} iterations, at least one of each")
+        if init.dim() != 5 or init.shape[0] != G or tuple(init.shape[2:]) != lat or not 1 <= init.shape[1] <= L.PC_MAX_EV:
+            raise ValueError(f"pc_window: init {tuple(init.shape)}, expected [G = {G}, n_ev <= {L.PC_MAX_EV}, C, H, W = "
+                             f"{list(lat)}]")
+        k = init.shape[1]
+        if 2 * k * G > self.MAX_PC_ROWS:
+            raise ValueError(f"pc_window: {G} timesteps x {k} directions are {2 * k * G} U-Net rows, at most "
+                             f"{self.MAX_PC_ROWS}")
+        for name, v in (("xts", xts), ("x0_preds", x0_preds)):
+            if v.numel() != G * N or tuple(v.shape[-3:]) != lat:
+                raise ValueError(f"pc_window: {name} {tuple(v.shape)} is not [G, C, H, W] = {[G, *lat]}")
+        if mask.numel() != N or tuple(mask.shape[-3:]) != lat:
+            raise ValueError(f"pc_window: mask {tuple(mask.shape)} is not [C, H, W] = {list(lat)}")
+        if pc_mode not in (1, 2, 3):
+            raise ValueError(f"pc_window: pc_mode {pc_mode!r} is not 1 (both), 2 (text) or 3 (uncond)")
+        if to_eigval.numel() != G:
+            raise ValueError(f"pc_window: to_eigval {tuple(to_eigval.shape)} for {G} timesteps")
+        if cond_text.rows != 1 or cond_uncond.rows != 1:
+            raise ValueError(f"pc_window: cond_text / cond_uncond have {cond_text.rows} / {cond_uncond.rows} rows, one each "
+                             f"(the prompt pair is shared by every timestep and direction)")
+        groups = [cond_uncond.repeat(k), cond_text.repeat(k)]
+        v_pred = int(s.config.prediction_type == "v_prediction")
+        L0, L1 = self._ctx_lens(groups)
+        S = len([it for it in range(iters) if it > 15 and it % 10 == 0])
+        key = ("pc_window", G, k, iters, L0, L1, v_pred, int(pc_mode), float(const), float(cfg_tar),
+               self._arith_for(2 * k * G))
+        plan = self._get_plan(key)
+        if plan is None:
+            f32 = dict(device=self.device, dtype=torch.float32)
+            plan = self._plans[key] = dict(
+                state=torch.zeros(4, dtype=torch.int32, device=self.device),      # the iteration counter
+                zero=torch.zeros(4, dtype=torch.int32, device=self.device),       # the time table is not stepped
+                ts=torch.zeros(G, dtype=torch.int64, device=self.device),
+                probe=torch.empty((G, k, *lat), **f32), previous=torch.empty((G, k, *lat), **f32),
+                jd=torch.empty((G, k, *lat), **f32), unit=torch.empty((G, k, *lat), **f32),
+                xt=torch.empty((G, *lat), **f32), x0p=torch.empty((G, *lat), **f32), mask=torch.empty(lat, **f32),
+                tab=torch.zeros((G, L.PC_TAB_STRIDE), **f32), stats=torch.zeros((2, iters, G, k), **f32),
+                snap_vec=torch.zeros((max(S, 1), G, k, *lat), **f32), snap_val=torch.zeros((max(S, 1), G, k), **f32))
+            eng = plan["eng"] = self.unet(2 * k * G, L0, L1)          # no CFG row sharing: every row has its own input
+            pre, post = Tape(self.device), Tape(self.device)
+            shape = dict(G=G, k=k, C=self.C, HW=self.H * self.W)
+            pre.pc_probe(x_in=eng.x_in, xt=plan["xt"], probe=plan["probe"], tab=plan["tab"], mode=int(pc_mode), **shape)
+            post.pc_jacobian(eps=eng.eps, xt=plan["xt"], probe=plan["probe"], tab=plan["tab"], x0_pred=plan["x0p"],
+                             mask=plan["mask"], jd=plan["jd"], cfg=float(cfg_tar), v_pred=v_pred, **shape)
+            post.pc_orthonormalise(jd=plan["jd"], mask=plan["mask"], unit=plan["unit"], previous=plan["previous"],
+                                   probe=plan["probe"], state=plan["state"], stats=plan["stats"], tab=plan["tab"], G=G, k=k,
+                                   N=N, iters=iters, const=float(const), snap_vec=plan["snap_vec"] if S else None,
+                                   snap_val=plan["snap_val"] if S else None, S=S)
+            post.advance(plan["state"])
+            pre.finalize()
+            post.finalize()
+            plan["pre"], plan["post"] = pre, post
+        eng, pre, post = plan["eng"], plan["pre"], plan["post"]
+        dev = lambda v: v.to(self.device, torch.float32)                                          # noqa: E731
+        plan["xt"].copy_(dev(xts).reshape(G, *lat))
+        plan["x0p"].copy_(dev(x0_preds).reshape(G, *lat))
+        plan["mask"].copy_(dev(mask).reshape(lat))
+        # the start of get_eigenvectors: probe = start * mask * const, previous = its copy
+        plan["probe"].copy_(dev(init) * plan["mask"] * const)
+        plan["previous"].copy_(plan["probe"])
+        tab = torch.zeros(G, L.PC_TAB_STRIDE, dtype=torch.float32)
+        for g, t in enumerate(ts):
+            c = step_coefficients(s, t, eta)
+            tab[g, 0] = torch.sqrt(s.alphas_cumprod[t])           # forward_directional's displacement scale
+            tab[g, 1], tab[g, 2] = c[0], c[1]
+        tab[:, 3] = to_eigval.detach().to("cpu", torch.float32).reshape(G)
+        plan["tab"].copy_(tab)
+        plan["ts"].copy_(torch.tensor(ts, dtype=torch.int64))
+        plan["stats"].zero_()
+        self._set_cond(eng, groups, repeat=G)
+        # every replay reads the same G timesteps: the table is the plan's own, stepped by a counter that stays 0
+        self._patch_time(eng, plan["ts"], G, 2 * k, state=plan["zero"])
+        plan["state"].zero_()
+
+        def body():
+            pre.run()
+            eng.tape.run()
+            post.run()
+        self._run_graph(body, iters, use_graph, plan)
+        return dict(unit=plan["unit"].clone(), probe=plan["probe"].clone(), in_norm=plan["stats"][0].clone(),
+                    in_corr=plan["stats"][1, :iters - 1].clone(), snap_vec=plan["snap_vec"][:S].clone(),
+                    snap_val=plan["snap_val"][:S].clone())
 
     # ------------------------------------------------------------------ A16: DDIM baseline
     @torch.inference_mode()

@@ -1,8 +1,10 @@
 """Unsupervised PC extraction for a real clip (BASELINE config 4): the body of the reference's
 code/main_pc_extract_inv.py:95-262 without wandb / plotting -- invert the clip with the edit-friendly DDPM
 inversion, replay the recorded noise maps with `forward_directional`, and inside the drift window run the
-subspace iteration (`get_eigenvectors`) at every timestep.  The checkpoint written by `save_extraction` has the
-reference's `.pt` layout (keys eigdata / args / corrs / in_corrs / latents / in_norms / xts; per timestep
+subspace iteration (`get_eigenvectors`) at every timestep -- or, with `--timestep_group G` above 1, replay the whole
+trajectory first and run the iteration for G window timesteps at a time (`get_eigenvectors_window`: one U-Net call of
+batch 2 * n_evs * G per iteration, the algebra in kernels of the same captured loop).  The checkpoint written by
+`save_extraction` has the reference's `.pt` layout (keys eigdata / args / corrs / in_corrs / latents / in_norms / xts; per timestep
 eigvec / eigval / interm_eigvecs / interm_eigvals / it / ts / norm_factor), so main_pc_apply_drift of either
 code base can read it.
 
@@ -24,15 +26,25 @@ def _default_fns():
     from .ddm_inversion.inversion_utils import inversion_forward_process
     from .utils import get_text_embeddings
     return SimpleNamespace(forward_directional=pc_drift.forward_directional, get_eigenvectors=pc_drift.get_eigenvectors,
-                           PCStreamChoice=pc_drift.PCStreamChoice, inversion_forward_process=inversion_forward_process,
-                           get_text_embeddings=get_text_embeddings)
+                           get_eigenvectors_window=pc_drift.get_eigenvectors_window, PCStreamChoice=pc_drift.PCStreamChoice,
+                           inversion_forward_process=inversion_forward_process, get_text_embeddings=get_text_embeddings)
 
 
 def extract_pcs(ldm_stable, w0: torch.Tensor, args, fns=None, checkpoint_cb=None):
     """main_pc_extract_inv.py:100-256.  `args` carries the reference's argparse fields (source_prompt,
     target_neg_prompt, cfg_tar, num_diffusion_steps, drift_start, drift_end, const, n_evs, iters, patch,
-    corr_to_swap, dry, eta, numerical_fix, double_precision, pc_mode).  Returns the checkpoint dict."""
+    corr_to_swap, dry, eta, numerical_fix, double_precision, pc_mode) and optionally `timestep_group` (default 1: the
+    reference's order, one timestep at a time; G > 1: the trajectory is replayed first, then the window runs G timesteps
+    per `get_eigenvectors_window` call and `checkpoint_cb` is called once per finished group).  Returns the checkpoint dict."""
     fns = fns or _default_fns()
+    group = getattr(args, "timestep_group", 1)
+    group = 1 if group is None else int(group)
+    if group < 1:
+        raise ValueError(f"extract_pcs: timestep_group {group} < 1")
+    if group > 1 and args.double_precision:
+        raise NotImplementedError("extract_pcs: timestep_group > 1 with double_precision=True: the native path is fp32")
+    if group > 1 and getattr(ldm_stable, "kind", None) == "stable_audio":
+        raise NotImplementedError("extract_pcs: timestep_group > 1: Stable Audio is not supported (AudioLDM, AudioLDM2, TANGO)")
     timesteps = ldm_stable.model.scheduler.timesteps
     if args.drift_start is None:
         args.drift_start = args.num_diffusion_steps
@@ -67,35 +79,52 @@ def extract_pcs(ldm_stable, w0: torch.Tensor, args, fns=None, checkpoint_cb=None
         return {"eigdata": eigdata, "args": args, "corrs": corrs, "in_corrs": in_corrs, "latents": latents,
                 "in_norms": in_norms, "xts": xts}
 
+    def record(it, t, eigvecs, eigval, in_corr, in_norm, interm_eigvecs, interm_eigvals):
+        nonlocal prev_pc
+        if it > drift_start_it:
+            # keep the sign of every PC consistent along the trajectory (main_pc_extract_inv.py:204-212)
+            corr = (prev_pc.reshape(args.n_evs, -1) @ eigvecs.reshape(args.n_evs, -1).T).diag()
+            for ev_num in range(args.n_evs):
+                if corr[ev_num] <= -args.corr_to_swap:
+                    eigvecs[ev_num] *= -1
+                    corr[ev_num] *= -1
+            corrs.append(corr)
+        prev_pc = eigvecs
+        in_corrs.append(in_corr)
+        in_norms.append(in_norm)
+        eigdata[t.item()] = {
+            "eigvec": eigvecs.detach().cpu(),
+            "eigval": eigval.detach().cpu(),
+            "interm_eigvecs": {k: v.detach().cpu() for k, v in interm_eigvecs.items()},
+            "interm_eigvals": {k: v.detach().cpu() for k, v in interm_eigvals.items()},
+            "it": it,
+            "ts": args.num_diffusion_steps - it,
+            "norm_factor": torch.sqrt(ldm_stable.model.scheduler.alphas_cumprod[t])}
+
+    window = []                         # timestep_group > 1: (it, t, x_t, x0_hat) of the window steps
     for it, t in enumerate(timesteps):
         xt_m1, x0_pred = fns.forward_directional(ldm_stable, xt, t, latents[it + 1], uncond_emb, text_emb, args.cfg_tar,
                                                  eta=args.eta, double_precision=args.double_precision)
         if not args.dry and drift_start_it <= it < drift_end_it:
-            eigvecs, eigval, in_corr, in_norm, interm_eigvecs, interm_eigvals = fns.get_eigenvectors(
-                ldm_stable, xt, text_emb, uncond_emb, latents[it + 1], mask, t, x0_pred, pc_mode, args.const,
-                args.cfg_tar, args.iters, args.double_precision, args.eta, args.n_evs)
-            if it > drift_start_it:
-                # keep the sign of every PC consistent along the trajectory (main_pc_extract_inv.py:204-212)
-                corr = (prev_pc.reshape(args.n_evs, -1) @ eigvecs.reshape(args.n_evs, -1).T).diag()
-                for ev_num in range(args.n_evs):
-                    if corr[ev_num] <= -args.corr_to_swap:
-                        eigvecs[ev_num] *= -1
-                        corr[ev_num] *= -1
-                corrs.append(corr)
-            prev_pc = eigvecs
-            in_corrs.append(in_corr)
-            in_norms.append(in_norm)
-            eigdata[t.item()] = {
-                "eigvec": eigvecs.detach().cpu(),
-                "eigval": eigval.detach().cpu(),
-                "interm_eigvecs": {k: v.detach().cpu() for k, v in interm_eigvecs.items()},
-                "interm_eigvals": {k: v.detach().cpu() for k, v in interm_eigvals.items()},
-                "it": it,
-                "ts": args.num_diffusion_steps - it,
-                "norm_factor": torch.sqrt(ldm_stable.model.scheduler.alphas_cumprod[t])}
+            if group > 1:
+                window.append((it, t, xt, x0_pred))
+            else:
+                record(it, t, *fns.get_eigenvectors(
+                    ldm_stable, xt, text_emb, uncond_emb, latents[it + 1], mask, t, x0_pred, pc_mode, args.const,
+                    args.cfg_tar, args.iters, args.double_precision, args.eta, args.n_evs))
         xt = xt_m1
         xts.append(xt.detach().clone())
-        if checkpoint_cb is not None and it % 10 == 0:
+        if checkpoint_cb is not None and it % 10 == 0 and group == 1:
+            checkpoint_cb(state())
+    # the window steps are independent of each other; record() applies the sign rule to the finished vectors, in order
+    for lo in range(0, len(window), group):
+        part = window[lo:lo + group]                            # the last group may be shorter
+        found = fns.get_eigenvectors_window(
+            ldm_stable, [w[2] for w in part], text_emb, uncond_emb, mask, [w[1] for w in part], [w[3] for w in part],
+            pc_mode, args.const, args.cfg_tar, args.iters, args.eta, args.n_evs)
+        for (it, t, _, _), res in zip(part, found):
+            record(it, t, *res)
+        if checkpoint_cb is not None:
             checkpoint_cb(state())
     out = state()
     out["final"] = xt
@@ -134,6 +163,8 @@ def build_parser():
     p.add_argument("-p", "--patch", nargs=2, default=None, type=int)
     p.add_argument("-t", "--iters", type=int, default=50)
     p.add_argument("-d", "--dry", action="store_true")
+    p.add_argument("--timestep_group", type=int, default=1,
+                   help="window timesteps per batched subspace iteration (1: one timestep at a time, the reference's order)")
     p.add_argument("--allow_synthetic", action="store_true",
                    help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
                         "(benchmarking only: the output is noise)")
@@ -153,7 +184,10 @@ def finish_args(args):
 def main(argv: Optional[List[str]] = None):
     from .models import load_model
     from .utils import load_audio, set_reproducability, synthetic_clip, write_wav
-    args = finish_args(build_parser().parse_args(argv))
+    parser = build_parser()
+    args = finish_args(parser.parse_args(argv))
+    if args.timestep_group < 1:
+        parser.error(f"--timestep_group {args.timestep_group} < 1")
     set_reproducability(args.seed, extreme=False)
     device = f"cuda:{args.device_num}"
     torch.cuda.set_device(args.device_num)

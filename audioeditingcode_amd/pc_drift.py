@@ -129,6 +129,54 @@ def get_eigenvectors(ldm_stable, xt: torch.Tensor, text_emb: PromptEmbeddings, u
     return probe / const, lengths * to_eigval, in_corr, in_norm, interm_eigvecs, interm_eigvals
 
 
+_PC_MODE_CODE = {PCStreamChoice.BOTH: 1, PCStreamChoice.TEXT: 2, PCStreamChoice.UNCOND: 3}
+
+
+def get_eigenvectors_window(ldm_stable, xts, text_emb: PromptEmbeddings, uncond_emb: PromptEmbeddings, mask: torch.Tensor,
+                            ts, x0_preds, pc_mode: PCStreamChoice = PCStreamChoice.BOTH, const: float = 1e-3,
+                            cfg_tar: float = 3, iters: int = 50, eta: float = 1, n_ev: int = 1,
+                            init_eigvecs=None) -> List[Tuple]:
+    """`get_eigenvectors` for several timesteps of one recorded trajectory at once.  The timesteps are independent (x_t and
+    x0_hat of the undrifted replay are known before the first iteration), so every power iteration is ONE U-Net call of
+    batch 2 * n_ev * len(ts), and the algebra around it -- masked lengths, the Householder QR, the sort, the statistics --
+    runs in kernels inside the same captured loop (EditEngine.pc_window): the host reads nothing until the last iteration.
+    xts / x0_preds: one [1, C, H, W] tensor per timestep of `ts`; init_eigvecs: None (randn_like per timestep, in order,
+    with the shape get_eigenvectors draws) or one start tensor per timestep.
+    Returns one get_eigenvectors tuple per timestep: same contents, shapes, dtypes and devices."""
+    if getattr(ldm_stable, "kind", None) not in ("audioldm", "audioldm2", "tango"):
+        raise NotImplementedError("get_eigenvectors_window: Stable Audio is not supported (AudioLDM, AudioLDM2, TANGO; "
+                                  "timestep_group 1 runs get_eigenvectors)")
+    if getattr(ldm_stable, "double_precision", False):
+        raise NotImplementedError("get_eigenvectors_window: double_precision=True: the native path is fp32")
+    k, G = int(n_ev), len(ts)
+    if G < 1 or len(xts) != G or len(x0_preds) != G or (init_eigvecs is not None and len(init_eigvecs) != G):
+        raise ValueError(f"get_eigenvectors_window: {len(xts)} xts and {len(x0_preds)} x0_preds for {G} timesteps")
+    xt0 = xts[0]
+    C, H, W = xt0.shape[-3:]
+    shape = (k, C, H, W)
+    starts = []
+    for g in range(G):                  # one draw per timestep, in window order, as the per-timestep path makes them
+        like = expand_for_evs(xts[g], k) if k > 1 else xts[g]
+        starts.append(torch.randn_like(like) if init_eigvecs is None else init_eigvecs[g].to(xt0.device))
+    to_eigval = torch.stack([ldm_stable.get_sigma(int(t)) ** 2 / const for t in ts])
+    out = ldm_stable.editor(H, W).pc_window(
+        torch.stack([x.reshape(C, H, W) for x in xts]), torch.stack([x.reshape(C, H, W) for x in x0_preds]),
+        mask.reshape(C, H, W), [int(t) for t in ts], _to_cond(ldm_stable, text_emb), _to_cond(ldm_stable, uncond_emb),
+        torch.stack([v.reshape(shape) for v in starts]), to_eigval, pc_mode=_PC_MODE_CODE[PCStreamChoice(pc_mode.value)],
+        const=const, cfg_tar=float(cfg_tar), iters=iters, eta=eta)
+    to_eigval = to_eigval.to(out["in_norm"].device)
+    snap_its = [it for it in range(iters) if it > 15 and it % 10 == 0]
+    lens = (lambda v: v) if k > 1 else (lambda v: v.reshape(()))             # n_ev = 1: 0-dim, as Tensor.norm() gives
+    results = []
+    for g in range(G):
+        in_norm = [lens(out["in_norm"][it, g]) for it in range(iters)]
+        in_corr = [out["in_corr"][it, g] for it in range(iters - 1)]
+        results.append((out["probe"][g] / const, in_norm[-1] * to_eigval[g], in_corr, in_norm,
+                        {it: out["snap_vec"][j, g] for j, it in enumerate(snap_its)},
+                        {it: lens(out["snap_val"][j, g]) for j, it in enumerate(snap_its)}))
+    return results
+
+
 # ---------------------------------------------------------------------------------------------- applying a drift
 def _stored_pc(eigdata, t, timesteps, num_diff_steps, use_specific_ts_pc, sub_iters, evals, device):
     """Direction(s) and eigenvalue(s) to use at timestep t: vectors may come from another timestep

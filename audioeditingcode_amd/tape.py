@@ -541,6 +541,28 @@ class Tape:
                   [fix_alpha, *c_imm], [cur, zs, eps, vecs, cfg, coef, state, w, mask, par], name=name,
                   nbytes=4 * numel * (4 * a + has_noise + n_ev + 2 * int(fix_mode > 0)))
 
+    # ------------------------------------------------------------------ PC power iteration (csrc/pc.hip)
+    def pc_probe(self, *, x_in, xt, probe, tab, G, k, C, HW, mode, name="pc_probe"):
+        """x_in rows [g][uncond x k | text x k] (NHWC) = xt[g] + probe[g, e] * tab[g, 0] on the streams `mode` displaces (1 both,
+        2 text, 3 uncond), xt[g] on the other (AED_OP_PC_PROBE); xt [G, N], probe [G, k, N] NCHW."""
+        self._add(L.OP_PC_PROBE, [G, k, C, HW, mode], [], [x_in, xt, probe, tab], name=name,
+                  nbytes=4 * G * k * C * HW * 4)
+
+    def pc_jacobian(self, *, eps, xt, probe, tab, x0_pred, mask, jd, G, k, C, HW, cfg, v_pred=0, name="pc_jacobian"):
+        """jd[g, e] = x0_hat(eps_u + cfg * (eps_c - eps_u), xt[g] + probe[g, e] * tab[g, 0]) * mask - x0_pred[g]
+        (AED_OP_PC_JACOBIAN); eps NHWC rows as pc_probe lays x_in out, everything else NCHW."""
+        self._add(L.OP_PC_JACOBIAN, [G, k, C, HW, v_pred], [cfg], [eps, xt, probe, tab, x0_pred, mask, jd], name=name,
+                  nbytes=4 * G * k * C * HW * 5)
+
+    def pc_orthonormalise(self, *, jd, mask, unit, previous, probe, state, stats, tab, G, k, N, iters, const,
+                          snap_vec=None, snap_val=None, S=0, it_imm=0, name="pc_orthonormalise"):
+        """The algebra of one power iteration for G slots x k directions (AED_OP_PC_ORTHONORMALISE; jd is overwritten):
+        unit, previous = unit, probe = unit * const; at iteration it = state[0] (None: it_imm) stats[0, it] = the lengths,
+        stats[1, it - 1] = <previous, unit> per direction, and snapshot slot it / 10 - 2 at it = 20, 30, ..."""
+        self._add(L.OP_PC_ORTHONORMALISE, [G, k, N, iters, S, it_imm], [const],
+                  [jd, mask, unit, previous, probe, state, stats, snap_vec, tab, snap_val], name=name,
+                  nbytes=4 * G * k * N * (4 * k + 8))
+
     # ------------------------------------------------------------------ Stable Audio Open ops (csrc/stable_audio.hip)
     def rotary(self, x, cos, sin, *, M, N, H, D, R, ld=None, nsec=2, sec_stride=None, name="rotary"):
         """Rotate the first R features of every head of q (and k) inside a fused projection buffer x[M, ld], in place."""

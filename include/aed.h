@@ -108,6 +108,19 @@ enum aed_opcode {
                                  and its coefficient table (coef [R][steps][AED_COEF_STRIDE]).  Row v is bit-identical to
                                  AED_OP_REVERSE_STEP with P = 1, cfg_scalar = cfg[v], its own table row and its own z or none
                                  (EditEngine.edit_rows: edits, SDEdit and DDIM runs as rows of one loop)                   */
+    /* 31-33: one power iteration of the principal-component extraction (pc_drift.py:96-198) for G timesteps x k directions
+       at once (EditEngine.pc_window; csrc/pc.hip).  The loop-resident buffers probe / previous / jd / unit [G][k][N], xt and
+       x0_pred [G][N], mask [N] are NCHW, x_in / eps NHWC; tab [G][4] = {sqrt(abar_t), c0, c1, sigma_t^2 / const} per slot */
+    AED_OP_PC_PROBE = 31,     /* before the U-Net: x_in rows [g][uncond x k | text x k] = xt[g] + probe[g][e] * sqrt(abar_t[g])
+                                 on the streams pc_mode displaces, xt[g] on the other; bit-equal to fp32 torch              */
+    AED_OP_PC_JACOBIAN = 32,  /* after the U-Net: CFG combine, x0_hat of scheduler.step from the displaced input (epsilon or
+                                 v prediction), jd = x0_hat * mask - x0_pred[g]; bit-equal to fp32 torch                    */
+    AED_OP_PC_ORTHONORMALISE = 33, /* one workgroup per slot, fp64 sums in a fixed order: masked lengths of jd, a = (jd / len) *
+                                 mask, for k > 1 a Householder QR in LAPACK's sign convention (R_jj = -|x_j| when the pivot is
+                                 >= 0, signed zeros included) with Q formed explicitly, negated when prod diag R < 0, columns
+                                 normalised; directions sorted by len * sigma_t^2 / const, descending and stable; previous = unit,
+                                 probe = unit * const; in_norm / in_corr rows and the snapshots of iterations 20, 30, ... are
+                                 written from a device iteration counter.  k <= 8                                            */
     AED_OP_COUNT
 };
 

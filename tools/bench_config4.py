@@ -6,7 +6,10 @@ timesteps, then the drift applied per PC.  Prints ONE JSON line: seconds per run
 size-independent checks of the result (finiteness, positive descending eigenvalues, orthonormal PCs, power-iteration
 convergence, the drift moves the sample).
 
-    PYTHONPATH=. python tools/bench_config4.py [--iters 50] [--n_evs 4] [--T 200] [--drift_start 120] [--drift_end 80]"""
+    PYTHONPATH=. python tools/bench_config4.py [--iters 50] [--n_evs 4] [--T 200] [--drift_start 120] [--drift_end 80]
+                                               [--timestep_group 1]
+
+--timestep_group G > 1 extracts G window timesteps per batched subspace iteration (main_pc_extract_inv --timestep_group)."""
 import argparse
 import json
 import sys
@@ -22,6 +25,7 @@ ap.add_argument("--n_evs", type=int, default=4)
 ap.add_argument("--drift_start", type=int, default=120)
 ap.add_argument("--drift_end", type=int, default=80)
 ap.add_argument("--model_id", default="cvssp/audioldm2")
+ap.add_argument("--timestep_group", type=int, default=1)
 a = ap.parse_args()
 
 from audioeditingcode_amd import main_pc_apply_drift as papply, main_pc_extract_inv as pext, models    # noqa: E402
@@ -38,6 +42,7 @@ ex = pext.finish_args(Namespace(seed=1, cfg_tar=3, model_id=a.model_id, init_aud
                                 source_prompt=["a recording of a piano melody"], target_neg_prompt=[""], corr_to_swap=0.8,
                                 drift_start=a.drift_start, drift_end=a.drift_end, results_path="unused", const=1e-3,
                                 n_evs=a.n_evs, patch=None, iters=a.iters, dry=False))
+ex.timestep_group = a.timestep_group
 apa = Namespace(drift_start=a.drift_start, drift_end=a.drift_end, amount=1.5, use_specific_ts_pc=None, fix_alpha=None,
                 fade_length=0.0, evs=list(range(1, a.n_evs + 1)), combine_evs=False, evals_pt=None, rand_v=False,
                 shift_x0_for_np=True, sub_iters=None)
@@ -85,6 +90,6 @@ print(json.dumps(dict(
     seconds=dict(extract=t_ext, apply=t_app), unet_sample_forwards=fwd, unet_sample_forwards_per_s=fwd / (t_ext + t_app),
     config=dict(workload=f"BASELINE configs[3]: AudioLDM2 ({a.model_id}, seeded-random weights), 10 s clip, T={a.T}, "
                          f"n_evs={a.n_evs}, iters={a.iters}, drift window {a.drift_start}->{a.drift_end}, amount 1.5, "
-                         f"PCs applied one by one"),
+                         f"PCs applied one by one", timestep_group=a.timestep_group),
     checks=checks, checks_pass=ok)))
 sys.exit(0 if ok else 3)
