@@ -168,6 +168,9 @@ def build_parser():
     p.add_argument("--allow_synthetic", action="store_true",
                    help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
                         "(benchmarking only: the output is noise)")
+    p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
+                   help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
+                        "torchaudio's default resampler (HIP kernel)")
     return p
 
 
@@ -183,7 +186,7 @@ def finish_args(args):
 
 def main(argv: Optional[List[str]] = None):
     from .models import load_model
-    from .utils import load_audio, set_reproducability, synthetic_clip, write_wav
+    from .utils import load_audio, resampler_label, set_reproducability, synthetic_clip, write_wav
     parser = build_parser()
     args = finish_args(parser.parse_args(argv))
     if args.timestep_group < 1:
@@ -193,11 +196,14 @@ def main(argv: Optional[List[str]] = None):
     torch.cuda.set_device(args.device_num)
     ldm_stable = load_model(args.model_id, device, args.num_diffusion_steps, args.double_precision,
                             allow_synthetic=getattr(args, "allow_synthetic", False) or None)
-    print(f"weights: {ldm_stable.weights_source}; text conditioning: {ldm_stable.conditioning_source}")
     src = args.init_aud if args.init_aud else (synthetic_clip(), 16000)
+    method = None if getattr(args, "resampler", "auto") == "auto" else args.resampler
+    print(f"weights: {ldm_stable.weights_source}; text conditioning: {ldm_stable.conditioning_source}; "
+          f"resampler: {resampler_label(src, 16000, method)}")
     # (the reference's call site is stale here -- no stft=True, 3-tuple bound to x0, main_pc_extract_inv.py:110; SURVEY
     # quirk 10 -- the evident intent is implemented)
-    x0, _, _ = load_audio(src, ldm_stable.get_fn_STFT(), device=device, stft=True, model_sr=ldm_stable.get_sr())
+    x0, _, _ = load_audio(src, ldm_stable.get_fn_STFT(), device=device, stft=True, model_sr=ldm_stable.get_sr(),
+                          resampler=method)
     with torch.inference_mode():
         w0 = ldm_stable.vae_encode(x0)
     clip = os.path.basename(args.init_aud).split(".")[0] if args.init_aud else "synthetic"

@@ -13,7 +13,7 @@ import torch
 from .ddm_inversion.ddim_inversion import ddim_inversion, text2image_ldm_stable
 from .ddm_inversion.inversion_utils import inversion_forward_process, inversion_reverse_process
 from .models import load_model
-from .utils import load_audio, set_reproducability, synthetic_clip, write_wav
+from .utils import load_audio, resampler_label, set_reproducability, synthetic_clip, write_wav
 
 
 def edit_clip(ldm_stable, x0, source_prompt, target_prompt, target_neg_prompt, cfg_src, cfg_tar, T, tstart,
@@ -87,6 +87,9 @@ def main(argv=None):
     p.add_argument("--allow_synthetic", action="store_true",
                    help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
                         "(benchmarking only: the output is noise)")
+    p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
+                   help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
+                        "torchaudio's default resampler (HIP kernel)")
     args = p.parse_args(argv)
     args.eta = 1.0
     set_reproducability(args.seed, extreme=False)
@@ -95,7 +98,9 @@ def main(argv=None):
     ldm_stable = load_model(args.model_id, device, args.num_diffusion_steps, allow_synthetic=args.allow_synthetic or None)
     src = args.init_aud if args.init_aud else (synthetic_clip(), 16000)
     sa = "stable-audio" in args.model_id
-    x0, sr, duration = load_audio(src, ldm_stable.get_fn_STFT(), device=device, stft=not sa, model_sr=ldm_stable.get_sr())
+    method = None if args.resampler == "auto" else args.resampler
+    x0, sr, duration = load_audio(src, ldm_stable.get_fn_STFT(), device=device, stft=not sa, model_sr=ldm_stable.get_sr(),
+                                  resampler=method)
     t0 = time.time()
     audio, orig, _ = edit_clip(ldm_stable, x0, args.source_prompt, args.target_prompt, args.target_neg_prompt,
                                args.cfg_src, args.cfg_tar, args.num_diffusion_steps, args.tstart, args.mode,
@@ -103,7 +108,8 @@ def main(argv=None):
                                duration=duration)
     torch.cuda.synchronize()
     print(f"edited {duration:.1f} s clip in {time.time() - t0:.2f} s (weights: {ldm_stable.weights_source}; "
-          f"text conditioning: {ldm_stable.conditioning_source})")
+          f"text conditioning: {ldm_stable.conditioning_source}; "
+          f"resampler: {resampler_label(src, ldm_stable.get_sr() if sa else 16000, method)})")
     os.makedirs(args.results_path, exist_ok=True)
     # main_run.py:223-224 saves the whole [channels, n] tensor: mono for the mel families, stereo for Stable Audio
     audio, orig = (a if a.dim() == 2 else a.reshape(-1, a.shape[-1]) for a in (audio, orig))

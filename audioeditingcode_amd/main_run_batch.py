@@ -15,7 +15,7 @@ import torch
 from .batch import batch_records, decode_variants, inversion_reverse_clips, parse_manifest
 from .ddm_inversion.inversion_utils import inversion_forward_process
 from .models import load_model
-from .utils import load_audio, set_reproducability, synthetic_clip, write_wav
+from .utils import load_audio, resampler_label, set_reproducability, synthetic_clip, write_wav
 
 
 def parse_args(argv=None):
@@ -32,6 +32,9 @@ def parse_args(argv=None):
     p.add_argument("--allow_synthetic", action="store_true",
                    help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
                         "(benchmarking only: the output is noise)")
+    p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
+                   help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
+                        "torchaudio's default resampler (HIP kernel)")
     args = p.parse_args(argv)
     if "stable-audio" in args.model_id:
         p.error("Stable Audio is not supported by the batched clip loop (use main_run per edit)")
@@ -52,11 +55,15 @@ def main(argv=None):
     model = load_model(args.model_id, device, T, allow_synthetic=args.allow_synthetic or None)
     t0 = time.time()
     inversions, sr = [], None
+    method = None if args.resampler == "auto" else args.resampler
+    resamplers = []
     with torch.inference_mode():
         for c, clip in enumerate(args.clips):
             Z = max(v.tstart for k, v in args.edits if k == c)
             src = clip["init_aud"] if clip["init_aud"] else (synthetic_clip(seed=1234 + c), 16000)
-            x0, sr, _ = load_audio(src, model.get_fn_STFT(), device=device, stft=True, model_sr=model.get_sr())
+            x0, sr, _ = load_audio(src, model.get_fn_STFT(), device=device, stft=True, model_sr=model.get_sr(),
+                                   resampler=method)
+            resamplers.append(resampler_label(src, 16000, method))
             _, zs, wts, _ = inversion_forward_process(model, model.vae_encode(x0), etas=args.eta,
                                                       prompts=[clip["source_prompt"]], cfg_scales=args.cfg_src,
                                                       num_inference_steps=T, numerical_fix=True, schedule=args.schedule)
@@ -66,7 +73,8 @@ def main(argv=None):
         audio = [wav for g in groups for wav in decode_variants(model, g)]
     torch.cuda.synchronize()
     print(f"{len(args.edits)} edits of {len(args.clips)} clips in {time.time() - t0:.2f} s (weights: "
-          f"{model.weights_source}; text conditioning: {model.conditioning_source})")
+          f"{model.weights_source}; text conditioning: {model.conditioning_source}; "
+          f"resampler: {', '.join(sorted(set(resamplers)))})")
     os.makedirs(args.results_path, exist_ok=True)
     records = batch_records(args.clips, args.edits)
     for rec, wav in zip(records, audio):

@@ -13,7 +13,7 @@ import torch
 
 from .grid import METHODS, decode_variants, expand_grid_rows, grid_records, run_grid
 from .models import load_model
-from .utils import load_audio, set_reproducability, synthetic_clip, write_wav
+from .utils import load_audio, resampler_label, set_reproducability, synthetic_clip, write_wav
 
 
 def parse_args(argv=None):
@@ -36,6 +36,9 @@ def parse_args(argv=None):
     p.add_argument("--allow_synthetic", action="store_true",
                    help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
                         "(benchmarking only: the output is noise)")
+    p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
+                   help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
+                        "torchaudio's default resampler (HIP kernel)")
     args = p.parse_args(argv)
     if "stable-audio" in args.model_id:
         p.error("Stable Audio is not supported by the batched grid loop (use main_run per edit)")
@@ -60,7 +63,9 @@ def main(argv=None):
     T = args.num_diffusion_steps
     model = load_model(args.model_id, device, T, allow_synthetic=args.allow_synthetic or None)
     src = args.init_aud if args.init_aud else (synthetic_clip(), 16000)
-    x0, sr, duration = load_audio(src, model.get_fn_STFT(), device=device, stft=True, model_sr=model.get_sr())
+    method = None if args.resampler == "auto" else args.resampler
+    x0, sr, duration = load_audio(src, model.get_fn_STFT(), device=device, stft=True, model_sr=model.get_sr(),
+                                  resampler=method)
     t0 = time.time()
     with torch.inference_mode():
         w0 = model.vae_encode(x0)
@@ -68,7 +73,8 @@ def main(argv=None):
         audio = decode_variants(model, lat)
     torch.cuda.synchronize()
     print(f"{len(args.rows)} grid rows of a {duration:.1f} s clip in {time.time() - t0:.2f} s (weights: "
-          f"{model.weights_source}; text conditioning: {model.conditioning_source})")
+          f"{model.weights_source}; text conditioning: {model.conditioning_source}; "
+          f"resampler: {resampler_label(src, 16000, method)})")
     os.makedirs(args.results_path, exist_ok=True)
     records = grid_records(args.rows)
     for rec, wav in zip(records, audio):

@@ -24,13 +24,16 @@ def build_parser():
     p.add_argument("--allow_synthetic", action="store_true",
                    help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
                         "(benchmarking only: the output is noise)")
+    p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
+                   help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
+                        "torchaudio's default resampler (HIP kernel)")
     return p
 
 
 def main(argv: Optional[List[str]] = None):
     from .models import load_model
     from .sdedit import sdedit
-    from .utils import load_audio, set_reproducability, synthetic_clip, write_wav
+    from .utils import load_audio, resampler_label, set_reproducability, synthetic_clip, write_wav
     args = build_parser().parse_args(argv)
     args.eta = 1.0
     set_reproducability(args.seed, extreme=False)
@@ -40,10 +43,13 @@ def main(argv: Optional[List[str]] = None):
     torch.cuda.set_device(args.device_num)
     ldm_stable = load_model(args.model_id, device, args.num_diffusion_steps,
                             allow_synthetic=getattr(args, "allow_synthetic", False) or None)
-    print(f"weights: {ldm_stable.weights_source}; text conditioning: {ldm_stable.conditioning_source}")
     src = args.init_aud if args.init_aud else (synthetic_clip(), 16000)
+    method = None if getattr(args, "resampler", "auto") == "auto" else args.resampler
+    print(f"weights: {ldm_stable.weights_source}; text conditioning: {ldm_stable.conditioning_source}; "
+          f"resampler: {resampler_label(src, 16000, method)}")
     # (stale call site in the reference, main_run_sdedit.py:69 -- SURVEY quirk 10; the evident intent is implemented)
-    x0, _, _ = load_audio(src, ldm_stable.get_fn_STFT(), device=device, stft=True, model_sr=ldm_stable.get_sr())
+    x0, _, _ = load_audio(src, ldm_stable.get_fn_STFT(), device=device, stft=True, model_sr=ldm_stable.get_sr(),
+                          resampler=method)
     t0 = time.time()
     with torch.inference_mode():
         w0 = ldm_stable.vae_encode(x0)

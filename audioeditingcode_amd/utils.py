@@ -1,6 +1,7 @@
 """Audio I/O + helpers mirroring the reference's code/utils.py (load_audio :53-95, get_spec :49-50,
 set_reproducability :98-116, get_text_embeddings :217-231) and audioldm/audio/tools.py
-(normalize_wav :46-49, pad_wav :34-44, read_wav_file :52-64, _pad_spec :18-31, wav_to_fbank :67-85)."""
+(normalize_wav :46-49, pad_wav :34-44, read_wav_file :52-64, _pad_spec :18-31, wav_to_fbank :67-85), and the
+resampler both call (torchaudio.functional.resample at its defaults), restated: sinc_resample_bank / resample(method="sinc")."""
 import math
 import random
 import wave
@@ -45,18 +46,9 @@ def prepare_waveform(waveform_16k, segment_length):
 
 
 def read_wav(path) -> Tuple[np.ndarray, int]:
-    """Mono float waveform + sample rate.  torchaudio when present, else the stdlib wave module (PCM16/32)."""
-    try:
-        import torchaudio
-        w, sr = torchaudio.load(path)
-        return w.numpy()[0], sr
-    except ImportError:
-        with wave.open(path, "rb") as f:
-            sr, nch, sw, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
-            raw = f.readframes(n)
-        dt = {2: np.int16, 4: np.int32}[sw]
-        x = np.frombuffer(raw, dtype=dt).reshape(-1, nch).astype(np.float32) / float(np.iinfo(dt).max + 1)
-        return x[:, 0], sr
+    """Mono float waveform + sample rate: channel 0 of `read_wav_channels`, as the reference's `numpy()[0]` (tools.py:54)."""
+    w, sr = read_wav_channels(path)
+    return w[0], sr
 
 
 def read_wav_channels(path) -> Tuple[np.ndarray, int]:
@@ -82,9 +74,72 @@ def read_wav_channels(path) -> Tuple[np.ndarray, int]:
         return np.ascontiguousarray(x.reshape(-1, nch).T), sr
 
 
-def resample(w, sr, new_sr):
+SINC_BANK_LIMIT = 64 << 20          # bytes of one filter bank `sinc_resample_bank` still builds
+
+
+def sinc_resample_bank(orig: int, new: int):
+    """The filter bank of `torchaudio.functional.resample(w, orig, new)` at its defaults (sinc_interp_hann,
+    lowpass_filter_width 6, rolloff 0.99), restated from `_get_sinc_resample_kernel`: torch fp32 ops in torchaudio's own
+    order, so the bank is the one torchaudio computes for an fp32 waveform.  Returns (bank fp32 [n, taps], width, o, n) with
+    o, n the reduced rates and taps = 2*width + o (include/aed.h, aed_resample_sinc, has the closed form)."""
+    orig, new = int(orig), int(new)
+    if orig <= 0 or new <= 0:
+        raise ValueError(f"sample rates must be positive, got {orig} -> {new}")
+    g = math.gcd(orig, new)
+    o, n = orig // g, new // g
+    lowpass_filter_width, rolloff = 6, 0.99
+    base = min(o, n) * rolloff
+    width = math.ceil(lowpass_filter_width * o / base)
+    size = 4 * n * (2 * width + o)
+    if size > SINC_BANK_LIMIT:
+        raise ValueError(f"resampling {orig} -> {new} Hz reduces to the ratio {o}:{n}, whose sinc filter bank "
+                         f"([{n}, {2 * width + o}] fp32, {size / 2 ** 20:.0f} MiB) is over the {SINC_BANK_LIMIT >> 20} MiB limit")
+    idx = torch.arange(-width, width + o, dtype=torch.float32)[None, None] / o
+    t = torch.arange(0, -n, -1, dtype=torch.float32)[:, None, None] / n + idx
+    t *= base
+    t = t.clamp_(-lowpass_filter_width, lowpass_filter_width)
+    window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    t *= math.pi
+    scale = base / o
+    kernels = torch.where(t == 0, torch.tensor(1.0).to(t), t.sin() / t)
+    kernels *= window * scale
+    return kernels[:, 0], width, o, n
+
+
+def _resample_sinc(w, sr, new_sr, device):
+    """[channels, L] or [L] float32 -> same rank at the new rate.  On a GPU device: csrc/resample.hip, all channels in one
+    launch.  Otherwise torchaudio's own CPU op sequence (`_apply_sinc_resample_kernel`: pad, conv1d with stride o, cut)."""
+    bank, width, o, n = sinc_resample_bank(sr, new_sr)
+    x = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
+    x2 = x.reshape(-1, x.shape[-1])
+    channels, length = x2.shape
+    out_len = -(-n * length // o)
+    if device is not None and torch.device(device).type == "cuda":
+        from . import _lib as L
+        with torch.cuda.device(device):
+            xd = x2.to(device)
+            bank_t = bank.t().contiguous().to(device)
+            y = torch.empty(channels, out_len, dtype=torch.float32, device=device)
+            L.check(L.lib().aed_resample_sinc(xd.data_ptr(), channels, length, bank_t.data_ptr(), o, n, width, y.data_ptr(),
+                                              out_len, L.current_stream_ptr()), "aed_resample_sinc")
+            y = y.cpu()
+    else:
+        xp = torch.nn.functional.pad(x2, (width, width + o))
+        y = torch.nn.functional.conv1d(xp[:, None], bank[:, None], stride=o)
+        y = y.transpose(1, 2).reshape(channels, -1)[..., :out_len]
+    return y.reshape(x.shape[:-1] + (out_len,)).numpy()
+
+
+def resample(w, sr, new_sr, method=None, device=None):
+    """`method=None`: torchaudio when it is installed, else scipy's polyphase resampler (a different filter: a stand-in).
+    `method="sinc"`: the native restatement of torchaudio's default resampler (`sinc_resample_bank`), on the HIP kernel when
+    `device` is a GPU device and in host torch otherwise; takes [L] or [channels, L].  Returns float32 numpy."""
     if sr == new_sr:
         return w
+    if method == "sinc":
+        return _resample_sinc(w, sr, new_sr, device)
+    if method is not None:
+        raise ValueError(f"unknown resampling method {method!r} (None or 'sinc')")
     try:
         import torchaudio
         return torchaudio.functional.resample(torch.from_numpy(w)[None], orig_freq=sr, new_freq=new_sr)[0].numpy()
@@ -92,6 +147,25 @@ def resample(w, sr, new_sr):
         from scipy.signal import resample_poly
         g = math.gcd(sr, new_sr)
         return resample_poly(w, new_sr // g, sr // g).astype(np.float32)
+
+
+def resampler_label(src, target_sr, resampler=None):
+    """Which resampler `load_audio(src, ..., resampler=resampler)` runs for a clip (a path or a (waveform, rate) pair) that
+    has to end at `target_sr`: the line the CLIs print next to the weight and conditioning sources."""
+    if isinstance(src, str):
+        with wave.open(src, "rb") as f:
+            sr = f.getframerate()
+    else:
+        sr = src[1]
+    if sr == target_sr:
+        return "none: already at the model rate"
+    if resampler == "sinc":
+        return "sinc (native)"
+    try:
+        import torchaudio  # noqa: F401
+        return "torchaudio"
+    except ImportError:
+        return "scipy polyphase stand-in"
 
 
 def get_duration(path):
@@ -124,10 +198,12 @@ def get_spec(wav: torch.Tensor, fn_STFT) -> torch.Tensor:
 
 
 def load_audio(audio_path, fn_STFT, left: int = 0, right: int = 0, device: Optional[torch.device] = None,
-               return_wav: bool = False, stft: bool = False, model_sr: Optional[int] = None):
+               return_wav: bool = False, stft: bool = False, model_sr: Optional[int] = None,
+               resampler: Optional[str] = None):
     """code/utils.py:53-95: the AudioLDM/TANGO spectrogram branch (stft=True) and the Stable Audio raw-waveform branch
     (stft=False -> (waveform [channels, n] normalised to +-0.5 over all channels, model_sr, duration)).  `audio_path` may
-    also be a (waveform, sample_rate) pair for in-memory clips."""
+    also be a (waveform, sample_rate) pair for in-memory clips.  `resampler` is `resample`'s `method` (None: as before;
+    "sinc": the native restatement of torchaudio's resampler, on `device` when that is a GPU)."""
     if not stft:
         if isinstance(audio_path, str):
             wav, sr = read_wav_channels(audio_path)
@@ -136,7 +212,10 @@ def load_audio(audio_path, fn_STFT, left: int = 0, right: int = 0, device: Optio
             wav = np.asarray(wav, dtype=np.float32)
             wav = wav[None] if wav.ndim == 1 else wav
         if sr != model_sr:
-            wav = np.stack([resample(c, sr, model_sr) for c in wav])
+            if resampler is None:
+                wav = np.stack([resample(c, sr, model_sr) for c in wav])
+            else:
+                wav = resample(wav, sr, model_sr, method=resampler, device=device)     # all channels in one call
         w = torch.from_numpy(np.ascontiguousarray(wav)).float()
         w = w - torch.mean(w)                                   # utils.py:83-88
         w = w / (torch.max(torch.abs(w)) + 1e-8)
@@ -151,7 +230,7 @@ def load_audio(audio_path, fn_STFT, left: int = 0, right: int = 0, device: Optio
     else:
         mel, duration, wav = audio_path, None, None
     if wav is not None:
-        wav16 = resample(np.asarray(wav, dtype=np.float32), sr, 16000)
+        wav16 = resample(np.asarray(wav, dtype=np.float32), sr, 16000, method=resampler, device=device)
         fbank, wav_t = wav_to_fbank(wav16, target_length=int(duration * 102.4), fn_STFT=fn_STFT)
         mel = fbank.unsqueeze(0)
     c, h, w = mel.shape

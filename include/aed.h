@@ -268,6 +268,21 @@ int aed_sample_xts_from_x0(const float* x0, const float* noise, const float* sqr
  * once with this feed AED_OP_CONV_GEMM records with flag bits 6|7 (p[7] = q, p[9] = scales); csrc/conv_gemm_f8.hip.          */
 int aed_mx_quantize_rows(const float* src, void* q, void* scales, long long rows, int K, void* stream);
 
+/* The resampling the reference does before anything else (audioldm/audio/tools.py:55, code/utils.py:80):
+ * torchaudio.functional.resample with its defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99), restated from
+ * the published semantics.  With g = gcd(orig, new), o = orig/g (orig_reduced), n = new/g (new_reduced),
+ * base = min(o, n)*0.99 and width = ceil(6*o/base), the filter bank is K[p][k], phase p in [0, n), tap k in [0, taps),
+ * taps = 2*width + o:
+ *   t = clamp((-p/n + (k - width)/o) * base, -6, 6)      K[p][k] = sinc(pi*t) * cos^2(pi*t/12) * base/o,  sinc(0) = 1
+ * The host evaluates it (utils.sinc_resample_bank does so in fp32 with torchaudio's op order) and passes it TRANSPOSED:
+ * bank_t: DEVICE float[taps][n], bank_t[k][p] = K[p][k].  x [channels][len] -> y [channels][out_len], fp32 FMAs in ascending k:
+ *   y[c][q*n + p] = sum_k K[p][k] * x[c][q*o + k - width],   x = 0 outside [0, len)
+ * out_len must be ceil(n*len/o) (the convolution's surplus frame is cut).  All channels run in one launch.
+ * Refused: null pointers, non-positive sizes, out_len != ceil(n*len/o), more than 65535 channels, and a ratio whose block
+ * of 256 outputs spans more than 16384 input samples (255/n rounded up, times o, plus taps: about 55:1 downwards).      */
+int aed_resample_sinc(const float* x, int channels, int64_t len, const float* bank_t, int orig_reduced, int new_reduced,
+                      int width, float* y, int64_t out_len, void* stream);
+
 /* ----------------------------------------------------------------------------------------
  * Stable Audio Open (StableAudWrapper, models.py:1051-1354)
  * -------------------------------------------------------------------------------------- */
