@@ -13,7 +13,7 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#include "attn_params.h"
+#include "attn_tile.h"
 
 #define KV_TILE 64
 #define Q_TILE 64
@@ -187,8 +187,8 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnParams p) {
 // under the MFMAs, LDS operations of one wave execute in order -> no workgroup barrier in the key loop.
 // KSPLIT = 1: the 4 waves of a workgroup take 4 consecutive query tiles (throughput regime, U-Net batch 2G);
 // KSPLIT = 4: they take the SAME query tile and every 4th key tile each, merged once through LDS (latency regime).
-typedef float f32x16a __attribute__((ext_vector_type(16)));
-
+// The workgroup order, the tile maximum and the final store are those of attn_tile.h, shared with the split-bf16 kernels
+// of attention_x6.hip.
 template <int D, int KSPLIT>
 __global__ __launch_bounds__(256) void attention_t_kernel(AttnParams p) {
     constexpr int DT = (D + 31) / 32;              // 32-row tiles of O^T
@@ -204,17 +204,8 @@ __global__ __launch_bounds__(256) void attention_t_kernel(AttnParams p) {
     float* Ks = smem + wave * SLAB;
     float* Vt = Ks + 32 * KLD;
 
-    // XCD-aware order: the query tiles of one (batch, head) run on one XCD (they share that head's K/V in its L2)
     int qt, head, b;
-    {
-        const unsigned nx = gridDim.x, ny = gridDim.y, nwg = nx * ny * gridDim.z;
-        const unsigned orig = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-        const unsigned xcd = orig & 7u, q = nwg >> 3, r = nwg & 7u;
-        const unsigned id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-        qt = (int)(id % nx);
-        head = (int)((id / nx) % ny);
-        b = (int)(id / (nx * ny));
-    }
+    attn_wg_coords(qt, head, b);
     const int q0 = (KSPLIT == 1 ? qt * 128 + wave * 32 : qt * 32);
     const int hoff = head * D;
     const float* Q = p.q + (size_t)b * p.bsq + hoff;
@@ -232,7 +223,7 @@ __global__ __launch_bounds__(256) void attention_t_kernel(AttnParams p) {
             qf[j] = make_float4(v.x * p.scale, v.y * p.scale, v.z * p.scale, v.w * p.scale);
         }
     }
-    f32x16a oacc[DT];
+    af32x16 oacc[DT];
 #pragma unroll
     for (int c = 0; c < DT; ++c)
 #pragma unroll
@@ -288,7 +279,7 @@ __global__ __launch_bounds__(256) void attention_t_kernel(AttnParams p) {
         asm volatile("" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         // ---- S^T tile: 32 keys x 32 queries, K = D
-        f32x16a sacc;
+        af32x16 sacc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
 #pragma unroll
@@ -313,14 +304,7 @@ __global__ __launch_bounds__(256) void attention_t_kernel(AttnParams p) {
             for (int r = 0; r < 16; ++r)
                 if (k0 + (r & 3) + 8 * (r >> 2) + 4 * fh >= p.Nk) sacc[r] = -INFINITY;
         }
-        float mx = sacc[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sacc[r]);
-        {
-            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));       // the other 16 keys of this query
-        }
-        const float mn = fmaxf(m_run, mx);
+        const float mn = fmaxf(m_run, attn_tile_max(sacc));
         const float alpha = __expf(m_run - mn);
         m_run = mn;
         float rsum = 0.f;
@@ -386,25 +370,7 @@ __global__ __launch_bounds__(256) void attention_t_kernel(AttnParams p) {
                 for (int r = 0; r < 16; ++r) oacc[c][r] += src[2 + 16 * c + r] * aw;
         }
     }
-    // ---- finish: add the two lane halves' shares of l, normalise, store O[q][d] (4 consecutive d per register quad)
-    {
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
-        l_run = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-    }
-    const float inv = 1.0f / l_run;
-    const int qr = q0 + fi;
-    if (qr < p.Nq) {
-        float* O = p.o + (size_t)b * p.bso + hoff + (size_t)qr * p.ldo;
-#pragma unroll
-        for (int c = 0; c < DT; ++c)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                const int d0 = c * 32 + 8 * rq + 4 * fh;
-                if (d0 < D)
-                    *reinterpret_cast<float4*>(O + d0) = make_float4(oacc[c][4 * rq] * inv, oacc[c][4 * rq + 1] * inv,
-                                                                     oacc[c][4 * rq + 2] * inv, oacc[c][4 * rq + 3] * inv);
-            }
-    }
+    attn_store_ot<D>(p, oacc, l_run, b, hoff, q0, fi, fh);
 }
 
 template <int D, int KSPLIT>

@@ -21,12 +21,11 @@
 // values are 4 consecutive e of the operand order: one 8-byte LDS write per piece, no transposing scatter.
 // Pipeline: two LDS stages, one workgroup barrier per key tile; tile t+1 is split + written while the MFMAs of tile t run, tiles
 // t+2 / t+3 are in flight in registers.
-#include "attn_params.h"
+#include "attn_tile.h"
 
 typedef __bf16 abf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 abf16x2 __attribute__((ext_vector_type(2)));
 typedef float af32x2 __attribute__((ext_vector_type(2)));
-typedef float af32x16 __attribute__((ext_vector_type(16)));
 
 // (x0, x1) -> packed bf16 pieces {hi, mid, lo}; x == hi + mid + lo exactly (element 0 in the low half)
 __device__ __forceinline__ void ax6_split_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
@@ -63,10 +62,85 @@ __device__ __forceinline__ void ax6_mfma6(af32x16& acc, const abf16x8 (&a)[3], c
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
 }
 
+// What the product kernel and its reference body below share besides attn_tile.h: the stage geometry, the Q^T pieces, the
+// split + write of a loader item and the V^T zero fill.  Each kernel spells out its loaders, its bias read and its key
+// loop -- and the S^T / O^T blocks and the exp / sum / rescale statements: behind functions those compile to another
+// instruction order or another register count in at least one of the six kernels (profiles/attn_shared_tile.md).
+template <int D>
+struct ax6_geo {
+    static constexpr int NT = 256;                 // threads
+    static constexpr int NDB = D / 16;             // 16-wide d blocks of the S^T contraction
+    static constexpr int DT = (D + 31) / 32;       // 32-row tiles of O^T
+    static constexpr int KQ = NDB * 3 * 64;        // uint4 per K stage ([db][piece][key 32][h 2] x 16 B)
+    static constexpr int VQ = 2 * 3 * DT * 64;     // uint4 per V stage ([kb][piece][dt][d 32][h 2] x 16 B)
+    static constexpr int STAGE = KQ + VQ;
+    static constexpr int C4 = D / 4;               // float4 per K row
+    static_assert(D % 16 == 0 && 2 * STAGE * 16 <= 65536, "head dim");
+};
+
+// Q^T pieces (B operand of S^T): lane (query fi, half fh) holds Q[q0 + fi][16 db + 8 fh + e], pre-scaled
+template <int D>
+__device__ __forceinline__ void ax6_load_q(const AttnParams& p, const float* Q, int q0, int fi, int fh,
+                                           abf16x8 (&qp)[D / 16][3]) {
+    const float* qrow = Q + (size_t)min(q0 + fi, p.Nq - 1) * p.ldq + 8 * fh;
+#pragma unroll
+    for (int db = 0; db < D / 16; ++db) {
+        const float4 a = *reinterpret_cast<const float4*>(qrow + 16 * db);
+        const float4 c = *reinterpret_cast<const float4*>(qrow + 16 * db + 4);
+        const float x[8] = {a.x * p.scale, a.y * p.scale, a.z * p.scale, a.w * p.scale,
+                            c.x * p.scale, c.y * p.scale, c.z * p.scale, c.w * p.scale};
+        ax6_split8(x, qp[db]);
+    }
+}
+
+// K loader item (one float4 of a tile's K rows, item = 0 .. 8 D - 1) -> the three pieces in the K stage of st
+template <int D>
+__device__ __forceinline__ void ax6_put_k(uint4* st, int item, float x0, float x1, float x2, float x3) {
+    constexpr int C4 = ax6_geo<D>::C4;
+    const int key = item / C4, c4 = item % C4;
+    unsigned h0, m0, l0, h1, m1, l1;
+    ax6_split_pair(x0, x1, h0, m0, l0);
+    ax6_split_pair(x2, x3, h1, m1, l1);
+    // K[key][4 c4 + j]: d block c4 >> 2, lane half (c4 >> 1) & 1, e = 4 (c4 & 1) + j
+    uint2* dst = reinterpret_cast<uint2*>(st) + ((c4 >> 2) * 3 * 32 + key) * 4 + ((c4 >> 1) & 1) * 2 + (c4 & 1);
+    dst[0] = make_uint2(h0, h1);
+    dst[32 * 4] = make_uint2(m0, m1);
+    dst[2 * 32 * 4] = make_uint2(l0, l1);
+}
+
+// V loader item (4 consecutive keys of one channel, item = 0 .. 8 D - 1) -> the three pieces in the V stage of st
+template <int D>
+__device__ __forceinline__ void ax6_put_v(uint4* st, int item, float x0, float x1, float x2, float x3) {
+    constexpr int DT = ax6_geo<D>::DT;
+    const int kg = item / D, d = item - kg * D;
+    unsigned h0, m0, l0, h1, m1, l1;
+    ax6_split_pair(x0, x1, h0, m0, l0);
+    ax6_split_pair(x2, x3, h1, m1, l1);
+    // keys 4 kg + j of channel d: key block kg >> 2, g = kg & 3 -> lane half g & 1, e = 4 (g >> 1) + j
+    const int kb = kg >> 2, g = kg & 3;
+    uint2* dst = reinterpret_cast<uint2*>(st + ax6_geo<D>::KQ) + (((kb * 3) * DT + (d >> 5)) * 32 + (d & 31)) * 4 + (g & 1) * 2 +
+                 (g >> 1);
+    dst[0] = make_uint2(h0, h1);
+    dst[DT * 32 * 4] = make_uint2(m0, m1);
+    dst[2 * DT * 32 * 4] = make_uint2(l0, l1);
+}
+
+// rows d >= D of V^T are never staged: keep them zero (both stages)
+template <int D>
+__device__ __forceinline__ void ax6_zero_stages(uint4* lds, int tid) {
+    using G = ax6_geo<D>;
+    if constexpr (G::DT * 32 > D) {
+        for (int e = tid; e < 2 * G::STAGE; e += G::NT) lds[e] = make_uint4(0u, 0u, 0u, 0u);
+        __syncthreads();
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The product kernel.  Same pieces, same six products in the same order, same max / exp / sum order as
-// attention_x6_ref_kernel below (every output value is bit-identical to it); what differs is the vector-instruction count
-// around the MFMAs (census and measurements: profiles/attn_x6_valu_diet.md; -35 % vector instructions, 6-14 % of the time):
+// attention_x6_ref_kernel below (every output value is bit-identical to it; the steps above and those of attn_tile.h are
+// the same code in both, the MFMA blocks and the exp / sum statements are kept equal by hand); what differs is the
+// vector-instruction count around the MFMAs (census and measurements: profiles/attn_x6_valu_diet.md; -35 % vector
+// instructions, 6-14 % of the time):
 //   * K, V and the key bias come through buffer loads.  A thread's byte offsets inside a tile are computed ONCE; moving to
 //     the next tile advances the descriptor's base and shrinks its num_records in SGPRs.  num_records ends with the last
 //     valid key row of this head, so keys >= Nk and the dead prefetches past the last tile read 0 (they are masked to -inf
@@ -84,48 +158,21 @@ template <int V> struct ax6_c { static constexpr int value = V; };
 
 template <int D>
 __global__ __launch_bounds__(256, 2) void attention_x6_kernel(AttnParams p) {
-    constexpr int NT = 256;                        // threads
-    constexpr int NDB = D / 16;                    // 16-wide d blocks of the S^T contraction
-    constexpr int DT = (D + 31) / 32;              // 32-row tiles of O^T
-    constexpr int KQ = NDB * 3 * 64;               // uint4 per K stage ([db][piece][key 32][h 2] x 16 B)
-    constexpr int VQ = 2 * 3 * DT * 64;            // uint4 per V stage ([kb][piece][dt][d 32][h 2] x 16 B)
-    constexpr int STAGE = KQ + VQ;
-    constexpr int C4 = D / 4;                      // float4 per K row
+    using G = ax6_geo<D>;
+    constexpr int NT = G::NT, NDB = G::NDB, DT = G::DT, KQ = G::KQ, STAGE = G::STAGE, C4 = G::C4;
     constexpr int NI = (16 * D + NT - 1) / NT;     // loader items per thread: items [0, 8 D) are K, [8 D, 16 D) are V
-    static_assert(D % 16 == 0 && 2 * STAGE * 16 <= 65536, "head dim");
     __shared__ uint4 lds[2 * STAGE];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fi = lane & 31, fh = lane >> 5;
-    // XCD-aware order (attention.hip): the query tiles of one (batch, head) run on one XCD
     int qt, head, b;
-    {
-        const unsigned nx = gridDim.x, ny = gridDim.y, nwg = nx * ny * gridDim.z;
-        const unsigned orig = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-        const unsigned xcd = orig & 7u, q = nwg >> 3, r = nwg & 7u;
-        const unsigned id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-        qt = (int)(id % nx);
-        head = (int)((id / nx) % ny);
-        b = (int)(id / (nx * ny));
-    }
+    attn_wg_coords(qt, head, b);
     const int q0 = qt * 128 + wave * 32;
     const int hoff = head * D;
-    const float* Q = p.q + (size_t)b * p.bsq + hoff;
 
-    // Q^T pieces (B operand of S^T): lane (query fi, half fh) holds Q[q0 + fi][16 db + 8 fh + e], pre-scaled
     abf16x8 qp[NDB][3];
-    {
-        const float* qrow = Q + (size_t)min(q0 + fi, p.Nq - 1) * p.ldq + 8 * fh;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) {
-            const float4 a = *reinterpret_cast<const float4*>(qrow + 16 * db);
-            const float4 c = *reinterpret_cast<const float4*>(qrow + 16 * db + 4);
-            const float x[8] = {a.x * p.scale, a.y * p.scale, a.z * p.scale, a.w * p.scale,
-                                c.x * p.scale, c.y * p.scale, c.z * p.scale, c.w * p.scale};
-            ax6_split8(x, qp[db]);
-        }
-    }
+    ax6_load_q<D>(p, p.q + (size_t)b * p.bsq + hoff, q0, fi, fh, qp);
     af32x16 oacc[DT];
 #pragma unroll
     for (int c = 0; c < DT; ++c)
@@ -180,38 +227,14 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(AttnParams p) {
         vbase += vstep; vrem = max(vrem - vstep, 0);
     };
     auto stage_write = [&](uint4* st, const af32x4 (&rg)[NI]) {
-        uint2* k2 = reinterpret_cast<uint2*>(st);
-        uint2* v2 = reinterpret_cast<uint2*>(st + KQ);
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int item = tid + NT * i;
-            unsigned h0, m0, l0, h1, m1, l1;
-            if (is_k(i)) {
-                const int key = item / C4, c4 = item % C4;
-                ax6_split_pair(rg[i][0], rg[i][1], h0, m0, l0);
-                ax6_split_pair(rg[i][2], rg[i][3], h1, m1, l1);
-                // K[key][4 c4 + j]: d block c4 >> 2, lane half (c4 >> 1) & 1, e = 4 (c4 & 1) + j
-                uint2* dst = k2 + ((c4 >> 2) * 3 * 32 + key) * 4 + ((c4 >> 1) & 1) * 2 + (c4 & 1);
-                dst[0] = make_uint2(h0, h1);
-                dst[32 * 4] = make_uint2(m0, m1);
-                dst[2 * 32 * 4] = make_uint2(l0, l1);
-            } else if (is_v(i)) {
-                const int it = item - 8 * D, kg = it / D, d = it - kg * D;
-                ax6_split_pair(rg[i][0], rg[i][1], h0, m0, l0);
-                ax6_split_pair(rg[i][2], rg[i][3], h1, m1, l1);
-                // keys 4 kg + j of channel d: key block kg >> 2, g = kg & 3 -> lane half g & 1, e = 4 (g >> 1) + j
-                const int kb = kg >> 2, g = kg & 3;
-                uint2* dst = v2 + (((kb * 3) * DT + (d >> 5)) * 32 + (d & 31)) * 4 + (g & 1) * 2 + (g >> 1);
-                dst[0] = make_uint2(h0, h1);
-                dst[DT * 32 * 4] = make_uint2(m0, m1);
-                dst[2 * DT * 32 * 4] = make_uint2(l0, l1);
-            }
+            if (is_k(i)) ax6_put_k<D>(st, item, rg[i][0], rg[i][1], rg[i][2], rg[i][3]);
+            else if (is_v(i)) ax6_put_v<D>(st, item - 8 * D, rg[i][0], rg[i][1], rg[i][2], rg[i][3]);
         }
     };
-    if constexpr (DT * 32 > D) {                   // rows d >= D of V^T are never staged: keep them zero (both stages)
-        for (int e = tid; e < 2 * STAGE; e += NT) lds[e] = make_uint4(0u, 0u, 0u, 0u);
-        __syncthreads();
-    }
+    ax6_zero_stages<D>(lds, tid);
 
     // one key tile; u: LDS stage and register slot (static), MASKED: the tile may be ragged or dead
     auto tile = [&](auto uc, auto mc, const int t) {
@@ -243,20 +266,9 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(AttnParams p) {
                     sacc[4 * rq + e] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(srd_b, bo + 4u * (8 * rq + e), 0, 0));
         }
         if constexpr (MASKED) {
-            if (k0 + 32 > p.Nk) {                  // ragged last tile / dead tile (wave-uniform)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (k0 + (r & 3) + 8 * (r >> 2) + 4 * fh >= p.Nk) sacc[r] = -INFINITY;
-            }
+            if (k0 + 32 > p.Nk) attn_mask_tail(sacc, k0, fh, p.Nk);       // ragged last tile / dead tile (wave-uniform)
         }
-        float mx = sacc[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sacc[r]);
-        {
-            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));       // the other 16 keys of this query
-        }
-        const float mn = fmaxf(m_run, mx);
+        const float mn = fmaxf(m_run, attn_tile_max(sacc));
         const float alpha = __expf(m_run - mn);
         m_run = mn;
         float rsum = 0.f;
@@ -307,77 +319,35 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(AttnParams p) {
         tile(ax6_c<1>{}, ax6_c<1>{}, t0 + 1);
     }
 
-    // ---- finish: add the two lane halves' shares of l, normalise, store O[q][d] (4 consecutive d per register quad)
-    {
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
-        l_run = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-    }
-    const float inv = 1.0f / l_run;
-    const int qr = q0 + fi;
-    if (qr < p.Nq) {
-        float* O = p.o + (size_t)b * p.bso + hoff + (size_t)qr * p.ldo;
-#pragma unroll
-        for (int c = 0; c < DT; ++c)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                const int d0 = c * 32 + 8 * rq + 4 * fh;
-                if (d0 < D)
-                    *reinterpret_cast<float4*>(O + d0) = make_float4(oacc[c][4 * rq] * inv, oacc[c][4 * rq + 1] * inv,
-                                                                     oacc[c][4 * rq + 2] * inv, oacc[c][4 * rq + 3] * inv);
-            }
-    }
+    attn_store_ot<D>(p, oacc, l_run, b, hoff, q0, fi, fh);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The kernel as it was before the changes above, kept compiled as the bit reference of the product kernel (variant 4 of the
-// attention record: tests/test_gpu_attention_x6_diet.py, tools/attn_x6_diet_ab.py) and as the path for operands whose
-// span does not fit the 31-bit buffer offsets.  The engines never select it.
+// The reference body: the same tile steps behind the loaders and the key loop the kernel had before the changes above
+// (clamped pointer loads, K and V items in separate registers, the mask test in every tile).  It stays compiled as the bit
+// reference of the product kernel (variant 4 of the attention record: tests/test_gpu_attention_x6_diet.py,
+// tools/attn_x6_diet_ab.py) and as the path for operands whose span does not fit the 31-bit buffer offsets.  The engines
+// never select it.
 template <int D>
 __global__ __launch_bounds__(256, 2) void attention_x6_ref_kernel(AttnParams p) {
-    constexpr int NDB = D / 16;                    // 16-wide d blocks of the S^T contraction
-    constexpr int DT = (D + 31) / 32;              // 32-row tiles of O^T
-    constexpr int KQ = NDB * 3 * 64;               // uint4 per K stage ([db][piece][key 32][h 2] x 16 B)
-    constexpr int VQ = 2 * 3 * DT * 64;            // uint4 per V stage ([kb][piece][dt][d 32][h 2] x 16 B)
-    constexpr int STAGE = KQ + VQ;
-    constexpr int C4 = D / 4;                      // float4 per K row
+    using G = ax6_geo<D>;
+    constexpr int NDB = G::NDB, DT = G::DT, KQ = G::KQ, STAGE = G::STAGE, C4 = G::C4;
     constexpr int NK = (8 * D + 255) / 256;        // K loader items (one float4) per thread
     constexpr int NV = (8 * D + 255) / 256;        // V loader items (4 keys x 1 channel) per thread
-    static_assert(D % 16 == 0 && 2 * STAGE * 16 <= 65536, "head dim");
     __shared__ uint4 lds[2 * STAGE];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fi = lane & 31, fh = lane >> 5;
-    // XCD-aware order (attention.hip): the query tiles of one (batch, head) run on one XCD
     int qt, head, b;
-    {
-        const unsigned nx = gridDim.x, ny = gridDim.y, nwg = nx * ny * gridDim.z;
-        const unsigned orig = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
-        const unsigned xcd = orig & 7u, q = nwg >> 3, r = nwg & 7u;
-        const unsigned id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-        qt = (int)(id % nx);
-        head = (int)((id / nx) % ny);
-        b = (int)(id / (nx * ny));
-    }
+    attn_wg_coords(qt, head, b);
     const int q0 = qt * 128 + wave * 32;
     const int hoff = head * D;
-    const float* Q = p.q + (size_t)b * p.bsq + hoff;
     const float* K = p.k + (size_t)b * p.bsk + hoff;
     const float* V = p.v + (size_t)b * p.bsv + hoff;
     const float* bias = p.bias ? p.bias + (size_t)b * p.ld_bias : nullptr;
 
-    // Q^T pieces (B operand of S^T): lane (query fi, half fh) holds Q[q0 + fi][16 db + 8 fh + e], pre-scaled
     abf16x8 qp[NDB][3];
-    {
-        const float* qrow = Q + (size_t)min(q0 + fi, p.Nq - 1) * p.ldq + 8 * fh;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) {
-            const float4 a = *reinterpret_cast<const float4*>(qrow + 16 * db);
-            const float4 c = *reinterpret_cast<const float4*>(qrow + 16 * db + 4);
-            const float x[8] = {a.x * p.scale, a.y * p.scale, a.z * p.scale, a.w * p.scale,
-                                c.x * p.scale, c.y * p.scale, c.z * p.scale, c.w * p.scale};
-            ax6_split8(x, qp[db]);
-        }
-    }
+    ax6_load_q<D>(p, p.q + (size_t)b * p.bsq + hoff, q0, fi, fh, qp);
     af32x16 oacc[DT];
 #pragma unroll
     for (int c = 0; c < DT; ++c)
@@ -406,42 +376,20 @@ __global__ __launch_bounds__(256, 2) void attention_x6_ref_kernel(AttnParams p) 
         }
     };
     auto stage_write = [&](uint4* st, const float4 (&kr)[NK], const float (&vr)[NV][4]) {
-        uint2* k2 = reinterpret_cast<uint2*>(st);
-        uint2* v2 = reinterpret_cast<uint2*>(st + KQ);
 #pragma unroll
         for (int i = 0; i < NK; ++i) {
             const int item = tid + 256 * i;
             if (8 * D % 256 != 0 && item >= 8 * D) break;
-            const int key = item / C4, c4 = item % C4;
-            unsigned h0, m0, l0, h1, m1, l1;
-            ax6_split_pair(kr[i].x, kr[i].y, h0, m0, l0);
-            ax6_split_pair(kr[i].z, kr[i].w, h1, m1, l1);
-            // K[key][4 c4 + j]: d block c4 >> 2, lane half (c4 >> 1) & 1, e = 4 (c4 & 1) + j
-            uint2* dst = k2 + ((c4 >> 2) * 3 * 32 + key) * 4 + ((c4 >> 1) & 1) * 2 + (c4 & 1);
-            dst[0] = make_uint2(h0, h1);
-            dst[32 * 4] = make_uint2(m0, m1);
-            dst[2 * 32 * 4] = make_uint2(l0, l1);
+            ax6_put_k<D>(st, item, kr[i].x, kr[i].y, kr[i].z, kr[i].w);
         }
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int item = tid + 256 * i;
             if (8 * D % 256 != 0 && item >= 8 * D) break;
-            const int kg = item / D, d = item - kg * D;
-            unsigned h0, m0, l0, h1, m1, l1;
-            ax6_split_pair(vr[i][0], vr[i][1], h0, m0, l0);
-            ax6_split_pair(vr[i][2], vr[i][3], h1, m1, l1);
-            // keys 4 kg + j of channel d: key block kg >> 2, g = kg & 3 -> lane half g & 1, e = 4 (g >> 1) + j
-            const int kb = kg >> 2, g = kg & 3;
-            uint2* dst = v2 + (((kb * 3) * DT + (d >> 5)) * 32 + (d & 31)) * 4 + (g & 1) * 2 + (g >> 1);
-            dst[0] = make_uint2(h0, h1);
-            dst[DT * 32 * 4] = make_uint2(m0, m1);
-            dst[2 * DT * 32 * 4] = make_uint2(l0, l1);
+            ax6_put_v<D>(st, item, vr[i][0], vr[i][1], vr[i][2], vr[i][3]);
         }
     };
-    if constexpr (DT * 32 > D) {                   // rows d >= D of V^T are never staged: keep them zero (both stages)
-        for (int e = tid; e < 2 * STAGE; e += 256) lds[e] = make_uint4(0u, 0u, 0u, 0u);
-        __syncthreads();
-    }
+    ax6_zero_stages<D>(lds, tid);
 
     prefetch(0, kreg[0], vreg[0]);
     prefetch(1, kreg[1], vreg[1]);
@@ -477,19 +425,8 @@ __global__ __launch_bounds__(256, 2) void attention_x6_ref_kernel(AttnParams p) 
                     for (int e = 0; e < 4; ++e)
                         sacc[4 * rq + e] += bias[min(k0 + 8 * rq + 4 * fh + e, p.Nk - 1)];
             }
-            if (k0 + 32 > p.Nk) {                  // ragged last tile / dead tile (wave-uniform)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (k0 + (r & 3) + 8 * (r >> 2) + 4 * fh >= p.Nk) sacc[r] = -INFINITY;
-            }
-            float mx = sacc[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sacc[r]);
-            {
-                auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-                mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));       // the other 16 keys of this query
-            }
-            const float mn = fmaxf(m_run, mx);
+            if (k0 + 32 > p.Nk) attn_mask_tail(sacc, k0, fh, p.Nk);       // ragged last tile / dead tile (wave-uniform)
+            const float mn = fmaxf(m_run, attn_tile_max(sacc));
             const float alpha = __expf(m_run - mn);
             m_run = mn;
             float rsum = 0.f;
@@ -523,42 +460,16 @@ __global__ __launch_bounds__(256, 2) void attention_x6_ref_kernel(AttnParams p) 
         }
     }
 
-    // ---- finish: add the two lane halves' shares of l, normalise, store O[q][d] (4 consecutive d per register quad)
-    {
-        auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
-        l_run = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-    }
-    const float inv = 1.0f / l_run;
-    const int qr = q0 + fi;
-    if (qr < p.Nq) {
-        float* O = p.o + (size_t)b * p.bso + hoff + (size_t)qr * p.ldo;
-#pragma unroll
-        for (int c = 0; c < DT; ++c)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                const int d0 = c * 32 + 8 * rq + 4 * fh;
-                if (d0 < D)
-                    *reinterpret_cast<float4*>(O + d0) = make_float4(oacc[c][4 * rq] * inv, oacc[c][4 * rq + 1] * inv,
-                                                                     oacc[c][4 * rq + 2] * inv, oacc[c][4 * rq + 3] * inv);
-            }
-    }
-}
-
-template <int D>
-static int launch_ax6_ref(const AttnParams& p, int B, hipStream_t s) {
-    dim3 grid(aed_cdiv(p.Nq, 128), p.H, B);
-    hipLaunchKernelGGL((attention_x6_ref_kernel<D>), grid, dim3(256), 0, s, p);
-    AED_CHECK_HIP(hipGetLastError());
-    return 0;
+    attn_store_ot<D>(p, oacc, l_run, b, hoff, q0, fi, fh);
 }
 
 template <int D>
 static int launch_ax6(const AttnParams& p, int B, bool reference, hipStream_t s) {
     // buffer loads address bytes below 2 GB of one (batch, head)'s keys, the three dead prefetch tiles included
     const bool fits = ((long)p.Nk + 96) * (p.ldk > p.ldv ? p.ldk : p.ldv) * 4 < (1L << 31);
-    if (reference || !fits) return launch_ax6_ref<D>(p, B, s);
     dim3 grid(aed_cdiv(p.Nq, 128), p.H, B);
-    hipLaunchKernelGGL((attention_x6_kernel<D>), grid, dim3(256), 0, s, p);
+    if (reference || !fits) hipLaunchKernelGGL((attention_x6_ref_kernel<D>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((attention_x6_kernel<D>), grid, dim3(256), 0, s, p);
     AED_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -139,16 +139,21 @@ def test_attention(B, H, Nq, Nk, D, masked):
     _attention_case(B, H, Nq, Nk, D, masked, variant=0)
 
 
-@pytest.mark.parametrize("B,H,Nq,Nk,D,masked", [(1, 2, 40, 200, 16, False), (1, 1, 33, 97, 80, True)])
+@pytest.mark.parametrize("B,H,Nq,Nk,D,masked", [(1, 2, 40, 200, 16, False), (1, 1, 33, 97, 80, True),
+                                                 (1, 2, 33, 70, 32, True)])
 def test_attention_ragged_long_keys(B, H, Nq, Nk, D, masked):
-    """long-key kernels with key / query counts that are not multiples of their tiles"""
+    """long-key kernels with key / query counts that are not multiples of their tiles; the last case has fewer key tiles
+    (3) than key-split waves, so one wave enters the merge with m = -inf, l = 0"""
     _attention_case(B, H, Nq, Nk, D, masked, variant=0)
 
 
 @pytest.mark.parametrize("B,H,Nq,Nk,D,masked", [(16, 8, 512, 512, 32, False), (32, 8, 256, 256, 48, True),
-                                                 (40, 8, 128, 100, 64, True)])
+                                                 (40, 8, 128, 100, 64, True), (64, 8, 40, 97, 80, True),
+                                                 (64, 8, 33, 70, 16, False)])
 def test_attention_transposed_kernel_throughput_mode(B, H, Nq, Nk, D, masked):
-    """enough workgroups that every wave takes its own query tile (KSPLIT = 1; U-Net batch 2G of the inversion)"""
+    """enough workgroups that every wave takes its own query tile (KSPLIT = 1; U-Net batch 2G of the inversion); the last
+    two: d_head 80 (three O^T tiles, one zero-padded) and 16 (one partial O^T tile) with a ragged last key tile and
+    waves past Nq"""
     _attention_case(B, H, Nq, Nk, D, masked, variant=0)
 
 
