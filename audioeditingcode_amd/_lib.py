@@ -28,6 +28,8 @@ OP_NAMES = ["nop", "conv_gemm", "gn_stats", "gn_apply", "layernorm", "attention"
             "drift_step_variants", "reverse_step_rows"]
 # the power iteration of the PC extraction (csrc/pc.hip); tape.py's helpers name these records themselves
 OP_PC_PROBE, OP_PC_JACOBIAN, OP_PC_ORTHONORMALISE = 31, 32, 33
+# the multi-row Stable Audio solver step (csrc/stable_audio.hip); tape.sa_step_variants names its record itself
+OP_SA_STEP_VARIANTS = 34
 PC_TAB_STRIDE = 4           # floats per slot of the ops' table: sqrt(abar_t), c0, c1, sigma_t^2 / const
 PC_MAX_EV = 8               # directions AED_OP_PC_ORTHONORMALISE takes
 ACT_NONE, ACT_SILU, ACT_LEAKY, ACT_TANH, ACT_LOGCLAMP = range(5)
@@ -87,12 +89,14 @@ def lib():
         L.aed_resample_sinc.argtypes = [vp, ci, ctypes.c_int64, vp, ci, ci, ci, vp, ctypes.c_int64, vp]
         L.aed_sa_get_zs_from_xts.argtypes = [vp, vp, vp, vp, cf, fp, vp, ci, vp, vp, ctypes.c_int64, vp]
         L.aed_sa_reverse_step_with_custom_noise.argtypes = [vp, vp, vp, cf, fp, vp, vp, vp, ctypes.c_int64, vp]
+        L.aed_sa_reverse_step_variants.argtypes = [vp, vp, vp, ci, fp, ctypes.POINTER(ci), ci, vp, vp, vp, ctypes.c_int64, vp]
         for name in ("aed_launch", "aed_tape_run", "aed_tape_profile", "aed_graph_begin", "aed_graph_end",
                      "aed_graph_launch", "aed_graph_destroy", "aed_stream_create_cu_mask", "aed_stream_destroy",
                      "aed_cu_census", "aed_image_load", "aed_image_free", "aed_image_run", "aed_image_program",
                      "aed_image_buffer", "aed_image_copy_in", "aed_image_copy_out", "aed_event_create", "aed_event_record", "aed_event_elapsed_ms", "aed_event_destroy", "aed_get_zs_from_xts",
                      "aed_reverse_step_with_custom_noise", "aed_reverse_step_variants", "aed_reverse_step_clips", "aed_reverse_step_rows", "aed_drift_step_variants", "aed_sample_xts_from_x0", "aed_device_info",
-                     "aed_sa_get_zs_from_xts", "aed_sa_reverse_step_with_custom_noise", "aed_mx_quantize_rows", "aed_resample_sinc"):
+                     "aed_sa_get_zs_from_xts", "aed_sa_reverse_step_with_custom_noise", "aed_sa_reverse_step_variants",
+                     "aed_mx_quantize_rows", "aed_resample_sinc"):
             getattr(L, name).restype = ci
         if L.aed_version() != 4:
             raise AedError("libaed.so ABI version mismatch")
@@ -107,7 +111,7 @@ EXPORTS = ["aed_version", "aed_last_error", "aed_device_info", "aed_launch", "ae
            "aed_event_record", "aed_event_elapsed_ms", "aed_event_destroy", "aed_get_zs_from_xts",
            "aed_reverse_step_with_custom_noise", "aed_reverse_step_variants", "aed_reverse_step_clips", "aed_reverse_step_rows", "aed_drift_step_variants", "aed_sample_xts_from_x0",
            "aed_sa_get_zs_from_xts",
-           "aed_sa_reverse_step_with_custom_noise", "aed_mx_quantize_rows", "aed_resample_sinc"]
+           "aed_sa_reverse_step_with_custom_noise", "aed_sa_reverse_step_variants", "aed_mx_quantize_rows", "aed_resample_sinc"]
 
 
 def check(rc, what=""):

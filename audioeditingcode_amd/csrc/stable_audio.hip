@@ -2,6 +2,7 @@
 //   AED_OP_SA_STEP      CFG + StableAudWrapper.get_zs_from_xts / reverse_step_with_custom_noise
 //                       (/root/reference/code/models.py:1209-1271, :1282-1329): SDE-DPM-Solver++ of order 1 / 2 with the
 //                       previous data prediction kept ON THE DEVICE (the scheduler's `model_outputs` history)
+//   AED_OP_SA_STEP_VARIANTS  the reverse step of AED_OP_SA_STEP for the rows of K edits of one inversion, one launch
 //   AED_OP_ROTARY       partial rotary embedding of q and k inside the fused qkv buffer (DiT self-attention)
 //   AED_OP_SNAKE        Snake1d activation of the Oobleck VAE: x + sin^2(a x) / (b + 1e-9), per channel
 //   AED_OP_GAUSS_SAMPLE mean + (softplus(scale) + 1e-4) * noise (OobleckDiagonalGaussianDistribution.sample, models.py:1132-1133)
@@ -33,12 +34,38 @@ struct SAStep {
     float c[AED_SA_COEF_STRIDE];
 };
 
+// The scheduler's numbers of one step, read once per thread from a coefficient row (AED_SA_COEF_STRIDE floats).
+struct SACoef {
+    float c_skip, c_out, k1, k2, k3, inv_r0, half_k2;
+    bool second, zero_z;
+};
+__device__ __forceinline__ SACoef sa_coef(const float* c) {
+    return SACoef{c[1], c[2], c[3], c[4], c[5], c[6], 0.5f * c[4], c[7] > 1.5f, c[8] > 0.5f};
+}
+
+// The arithmetic of one element of one step, the ONLY statement of the solver expressions in this file: the single-row
+// kernel and the multi-row kernel both call it, which is what makes a row of the latter bit-identical to the former.
+// u / vc: the model's unconditional / conditional output (has_c false: u alone, empty source prompt); x: x_t; m1: the
+// previous data prediction.  mode 0 (inversion): xtm1 is the trajectory's x_{t-1}; the noise that explains it comes back
+// in zz and the numerically fixed x_{t-1} in xo.  mode 1 (reverse): zz is the noise to add on entry, xo is x_{t-1}.
+// Returns this step's data prediction.
+__device__ __forceinline__ float sa_step_math(const SACoef& k, int mode, float u, float vc, bool has_c, float cfg, float x,
+                                              float m1, float xtm1, float& zz, float& xo) {
+    const float v = has_c ? u + cfg * (vc - u) : u;                    // inversion_utils.py:97-102 with one prompt
+    const float d = k.c_skip * x + k.c_out * v;                        // scheduler.convert_model_output (v-prediction)
+    const float D1 = k.second ? k.inv_r0 * (d - m1) : 0.0f;
+    if (mode == 0) {
+        if (k.zero_z) zz = 0.0f;                                       // models.py:1235-1236
+        else if (!k.second) zz = ((xtm1 - k.k1 * x) - k.k2 * d) / k.k3;                      // models.py:1238-1241
+        else zz = (((xtm1 - k.k1 * x) - k.k2 * d) - k.half_k2 * D1) / k.k3;                  // models.py:1243-1255
+    }
+    xo = k.second ? ((k.k1 * x + k.k2 * d) + k.half_k2 * D1) + k.k3 * zz : (k.k1 * x + k.k2 * d) + k.k3 * zz;
+    return d;
+}
+
 __global__ __launch_bounds__(256) void sa_step_kernel(SAStep p) {
     const int s = p.state ? p.state[0] * p.s_mul + p.s_off : p.s_imm;
-    const float* c = p.coef ? p.coef + (size_t)s * AED_SA_COEF_STRIDE : p.c;
-    const float c_skip = c[1], c_out = c[2], k1 = c[3], k2 = c[4], k3 = c[5], inv_r0 = c[6];
-    const bool second = c[7] > 1.5f, zero_z = c[8] > 0.5f;
-    const float half_k2 = 0.5f * k2;
+    const SACoef k = sa_coef(p.coef ? p.coef + (size_t)s * AED_SA_COEF_STRIDE : p.c);
     const float* xt;
     float *xtm1 = nullptr, *z = nullptr, *extra = nullptr;
     if (p.mode == 0) {
@@ -55,23 +82,16 @@ __global__ __launch_bounds__(256) void sa_step_kernel(SAStep p) {
         if (p.zs) z = (p.explicit_ptrs || p.T <= 0) ? p.zs : p.zs + (size_t)(p.T - s - 1) * p.numel;   // T := number of zs
     }
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < p.numel; e += (size_t)gridDim.x * 256) {
-        const float u = p.v_u[e];
-        const float v = p.v_c ? u + p.cfg * (p.v_c[e] - u) : u;        // inversion_utils.py:97-102 with one prompt
-        const float x = xt[e];
-        const float d = c_skip * x + c_out * v;                        // scheduler.convert_model_output (v-prediction)
         const float m1 = p.hist[e];
-        const float D1 = second ? inv_r0 * (d - m1) : 0.0f;
+        float zz = (p.mode != 0 && z) ? z[e] : 0.0f, xo;
+        const float d = sa_step_math(k, p.mode, p.v_u[e], p.v_c ? p.v_c[e] : 0.0f, p.v_c != nullptr, p.cfg, xt[e], m1,
+                                     p.mode == 0 ? xtm1[e] : 0.0f, zz, xo);
         if (p.mode == 0) {
-            float zz;
-            if (zero_z) zz = 0.0f;                                     // models.py:1235-1236
-            else if (!second) zz = ((xtm1[e] - k1 * x) - k2 * d) / k3;                      // models.py:1238-1241
-            else zz = (((xtm1[e] - k1 * x) - k2 * d) - half_k2 * D1) / k3;                  // models.py:1243-1255
             z[e] = zz;
-            if (p.fix) xtm1[e] = second ? ((k1 * x + k2 * d) + half_k2 * D1) + k3 * zz : (k1 * x + k2 * d) + k3 * zz;
+            if (p.fix) xtm1[e] = xo;
             if (extra) extra[e] = m1;
         } else {
-            const float zz = z ? z[e] : 0.0f;
-            p.out[e] = second ? ((k1 * x + k2 * d) + half_k2 * D1) + k3 * zz : (k1 * x + k2 * d) + k3 * zz;
+            p.out[e] = xo;
         }
         p.hist[e] = d;
     }
@@ -121,6 +141,120 @@ extern "C" int aed_sa_reverse_step_with_custom_noise(const float* xt, const floa
     hipLaunchKernelGGL(sa_step_kernel, dim3(sa_grid(p.numel)), dim3(256), 0, (hipStream_t)stream, p);
     AED_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+// ------------------------------------------------------------------------------------ solver step for K edits of one clip
+// One reverse step of the `a` active rows [0, a) of cur [K][numel], all at the same loop step
+// (StableAudioEditEngine.edit_variants): the DiT's output is v [a uncond | a cond][numel], every row has its own guidance
+// scale (device float[a]), its own history row of hist [K][numel] and -- because a row that starts at tstart == T has no
+// history and takes its first step at order 1 while the others are at order 2 -- its own coefficient table, named by a
+// device int[a] into coef [R][steps][AED_SA_COEF_STRIDE].  The noise is shared: row Z - step - 1 of zs [Z][numel].  Row v
+// is sa_step_kernel in mode 1 on that row: the same sa_step_math on the same operands.
+// Grid: x walks element chunks, y is the row, so one row of the full-size latent (numel = 65536) and sixteen both put a
+// block on every CU.  16-byte accesses are used when every row start is 16-byte aligned (numel % 4 == 0 and aligned
+// bases) AND there are enough of them for a block per CU; otherwise 4-byte accesses, which at a = 1, numel = 65536 give
+// 256 blocks where float4 would give 64.
+#define AED_SA_ROWS_MAX_EXPLICIT 16
+struct SAVarStep {
+    const float* cur;     // [K][numel], rows [0, a) read
+    float* out;           // [K][numel], rows [0, a) written (may be cur)
+    const float* v;       // [2a][numel]
+    const float* cfg;     // [a]
+    float* hist;          // [K][numel]
+    const float* zs;      // [Z][numel] | one z (Z <= 0) | null
+    const float* coef;    // [R][steps][AED_SA_COEF_STRIDE]; null => the explicit form (c_row)
+    const int* ctab;      // [a] coefficient table of every row (nullable: table 0)
+    const int* state;     // device step counter (nullable -> s_imm)
+    size_t numel;
+    int a, Z, steps, s_mul, s_off, s_imm;
+    float c_row[AED_SA_ROWS_MAX_EXPLICIT][AED_SA_COEF_STRIDE];   // explicit form: one coefficient row per row
+};
+
+template <int VEC>
+__global__ __launch_bounds__(256) void sa_step_variants_kernel(SAVarStep p) {
+    const int s = p.state ? p.state[0] * p.s_mul + p.s_off : p.s_imm;
+    const int row = blockIdx.y;
+    const SACoef k = sa_coef(p.coef ? p.coef + ((size_t)(p.ctab ? p.ctab[row] : 0) * p.steps + s) * AED_SA_COEF_STRIDE
+                                    : p.c_row[row]);
+    const float cfg = p.cfg[row];
+    const size_t base = (size_t)row * p.numel;
+    const float* x = p.cur + base;
+    const float* vu = p.v + base;
+    const float* vc = p.v + ((size_t)p.a + row) * p.numel;
+    float* hist = p.hist + base;
+    float* out = p.out + base;
+    const float* z = !p.zs ? nullptr : (p.Z <= 0 ? p.zs : p.zs + (size_t)(p.Z - s - 1) * p.numel);
+    const size_t units = p.numel / VEC;                                // VEC == 4 only when numel % 4 == 0
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < units; e += (size_t)gridDim.x * 256) {
+        if constexpr (VEC == 4) {
+            const float4 xx = reinterpret_cast<const float4*>(x)[e], uu = reinterpret_cast<const float4*>(vu)[e];
+            const float4 cc = reinterpret_cast<const float4*>(vc)[e], mm = reinterpret_cast<const float4*>(hist)[e];
+            float4 zz = z ? reinterpret_cast<const float4*>(z)[e] : make_float4(0.0f, 0.0f, 0.0f, 0.0f), o, d;
+            d.x = sa_step_math(k, 1, uu.x, cc.x, true, cfg, xx.x, mm.x, 0.0f, zz.x, o.x);
+            d.y = sa_step_math(k, 1, uu.y, cc.y, true, cfg, xx.y, mm.y, 0.0f, zz.y, o.y);
+            d.z = sa_step_math(k, 1, uu.z, cc.z, true, cfg, xx.z, mm.z, 0.0f, zz.z, o.z);
+            d.w = sa_step_math(k, 1, uu.w, cc.w, true, cfg, xx.w, mm.w, 0.0f, zz.w, o.w);
+            reinterpret_cast<float4*>(out)[e] = o;
+            reinterpret_cast<float4*>(hist)[e] = d;
+        } else {
+            float zz = z ? z[e] : 0.0f, o;
+            const float d = sa_step_math(k, 1, vu[e], vc[e], true, cfg, x[e], hist[e], 0.0f, zz, o);
+            out[e] = o;
+            hist[e] = d;
+        }
+    }
+}
+
+static int launch_sa_variants(const SAVarStep& p, hipStream_t s, const char* what) {
+    AED_REQUIRE(p.cur && p.out && p.v && p.cfg && p.hist, "%s: null pointer", what);
+    AED_REQUIRE(p.a >= 1 && p.a <= 65535, "%s: %d rows", what, p.a);
+    if (p.numel == 0) return 0;
+    const size_t cus = (size_t)aed_num_cus();
+    const uintptr_t bases = (uintptr_t)p.cur | (uintptr_t)p.out | (uintptr_t)p.v | (uintptr_t)p.hist | (uintptr_t)p.zs;
+    const bool vec = p.numel % 4 == 0 && bases % 16 == 0 && (size_t)p.a * (p.numel / 1024) >= cus;
+    const size_t chunks = (p.numel / (vec ? 4 : 1) + 255) / 256;
+    const size_t cap = cus * 8 / p.a > 0 ? cus * 8 / p.a : 1;
+    const dim3 grid((unsigned)(chunks > cap ? cap : chunks), (unsigned)p.a);
+    if (vec) hipLaunchKernelGGL(sa_step_variants_kernel<4>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(sa_step_variants_kernel<1>, grid, dim3(256), 0, s, p);
+    AED_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// slots: p0=cur [K][numel] (rows [0, a) stepped)  p1=zs [Z][numel] | one z (Z = 0) | null  p2=v [2a][numel]
+//        p3=ctab int[a] (device; coefficient table of a row; null => table 0)  p4=cfg [a] (device)
+//        p5=coef [R][steps][AED_SA_COEF_STRIDE]  p6=state (nullable)  p7=out (null => in place into p0)  p8=hist [K][numel]
+//   i0,i1=numel lo/hi  i2=a  i3=Z  i4=s_imm  i5=steps (rows per coefficient table)  i6=R
+//   i7=s_mul i8=s_off (step = state*s_mul + s_off)
+int launch_sa_step_variants(const aed_op* op, hipStream_t s) {
+    SAVarStep p = {};
+    p.cur = (const float*)op->p[0]; p.zs = (const float*)op->p[1]; p.v = (const float*)op->p[2];
+    p.ctab = (const int*)op->p[3]; p.cfg = (const float*)op->p[4]; p.coef = (const float*)op->p[5];
+    p.state = (const int*)op->p[6]; p.out = op->p[7] ? (float*)op->p[7] : (float*)op->p[0]; p.hist = (float*)op->p[8];
+    p.numel = (size_t)(uint32_t)op->i[0] | ((size_t)(uint32_t)op->i[1] << 32);
+    p.a = op->i[2]; p.Z = op->i[3]; p.s_imm = op->i[4]; p.steps = op->i[5];
+    p.s_mul = op->i[7] > 0 ? op->i[7] : 1; p.s_off = op->i[8];
+    AED_REQUIRE(p.coef && op->i[6] >= 1 && p.steps >= 1, "sa_step_variants: %d coefficient tables of %d rows", op->i[6],
+                p.steps);
+    return launch_sa_variants(p, s, "sa_step_variants");
+}
+
+extern "C" int aed_sa_reverse_step_variants(const float* xt, const float* v, const float* cfg, int n_variants,
+                                            const float* coef_rows_host, const int* ctab_host, int n_tables, float* hist,
+                                            const float* z, float* prev_out, int64_t numel, void* stream) {
+    AED_REQUIRE(coef_rows_host && numel >= 0 && n_tables >= 1,
+                "aed_sa_reverse_step_variants: null coefficients, negative numel or no table");
+    AED_REQUIRE(n_variants >= 1 && n_variants <= AED_SA_ROWS_MAX_EXPLICIT, "aed_sa_reverse_step_variants: %d rows, at most %d",
+                n_variants, AED_SA_ROWS_MAX_EXPLICIT);
+    SAVarStep p = {};
+    p.cur = xt; p.out = prev_out; p.v = v; p.cfg = cfg; p.hist = hist; p.zs = z; p.Z = 0; p.a = n_variants;
+    p.numel = (size_t)numel; p.s_mul = 1;
+    for (int r = 0; r < n_variants; ++r) {
+        const int t = ctab_host ? ctab_host[r] : 0;
+        AED_REQUIRE(t >= 0 && t < n_tables, "aed_sa_reverse_step_variants: row %d names table %d of %d", r, t, n_tables);
+        for (int j = 0; j < AED_SA_COEF_STRIDE; ++j) p.c_row[r][j] = coef_rows_host[(size_t)t * AED_SA_COEF_STRIDE + j];
+    }
+    return launch_sa_variants(p, (hipStream_t)stream, "aed_sa_reverse_step_variants");
 }
 
 // ------------------------------------------------------------------------------------ rotary embedding (q and k in place)

@@ -23,7 +23,7 @@ import math
 import torch
 
 from . import _lib as L
-from .editing import LoopPlumbing
+from .editing import LoopPlumbing, variant_plan, variant_positions
 from .scheduler import sa_coefficient_table
 from . import tape as tape_mod
 from .tape import Tape
@@ -374,7 +374,8 @@ class OobleckDecoder(_OobleckBase):
 # =============================================================================================== loops
 class StableAudioEditEngine(LoopPlumbing):
     """Device-resident inversion / edit loops of the Stable Audio wrapper for ONE clip and ONE prompt per pass (the
-    reference's DiT call cannot take more: its global token is batch 1, models.py:1345-1349).
+    reference's DiT call cannot take more: its global token is batch 1, models.py:1345-1349); edit_variants runs K such
+    edits of one inversion as rows of one loop (DiTEngine takes a context and a global token per row).
 
     DiT batch rows per timestep: [uncond | cond] (cond dropped for an empty source prompt, inversion_utils.py:86).
     `mode="batched"` runs G timesteps per DiT call in the forward inversion -- legal for the same reason as in
@@ -565,3 +566,119 @@ class StableAudioEditEngine(LoopPlumbing):
             post.run()
         self._run_graph(body, Z if n_steps is None else max(0, min(int(n_steps), Z)), use_graph, plan)
         return cur.clone()
+
+    # ------------------------------------------------------------------ K edits of one inversion
+    MAX_VARIANTS = 8        # rows per edit_variants call; stable_audio_variants.py chunks longer lists (see edit_variants)
+
+    @staticmethod
+    def _ctx_rows(ctx, K, what):
+        """K tensors [1, S, Dc] from a list of K, or from one tensor with K rows or 1 (shared) row."""
+        if isinstance(ctx, (list, tuple)):
+            rows = list(ctx)
+            if len(rows) != K:
+                raise ValueError(f"edit_variants: {len(rows)} {what} contexts for {K} variants")
+        elif ctx.shape[0] == 1:
+            rows = [ctx] * K
+        elif ctx.shape[0] == K:
+            rows = [ctx[v:v + 1] for v in range(K)]
+        else:
+            raise ValueError(f"edit_variants: {what} has {ctx.shape[0]} rows for {K} variants")
+        if any(r.dim() != 3 or r.shape[0] != 1 for r in rows):
+            raise ValueError(f"edit_variants: every {what} context is one [1, S, Dc] tensor")
+        return rows
+
+    @torch.inference_mode()
+    def edit_variants(self, xts, zs, tstarts, ctx_tgt, ctx_neg, glob, cfg_tars, extra=None, first_order=False,
+                      use_graph=True):
+        """K edits of ONE inverted clip in one device-resident loop.  Variant v is `edit(xts, zs, tstarts[v], ctx_tgt[v],
+        ctx_neg[v], glob, cfg_tars[v], extra=extra, first_order=first_order)`; all share the trajectory xts [T+1, L, C],
+        the noise maps zs [>= max(tstarts), L, C], the inversion's extra [T, L, C] (channels-last, as invert() returns
+        them) and the global token.  ctx_tgt / ctx_neg: a list of K [1, S, Dc] tensors, or one tensor with K rows or 1
+        (shared) row.  Returns the edited latents [K, L, C] in the caller's order.
+
+        The variants run sorted by tstart, largest first (editing.variant_plan): the loop walks the max(tstart) steps in
+        segments between the distinct tstarts, and in each segment the active variants are a prefix [0, a) of the sorted
+        list whose DiT batch is [a negative | a target] rows (batch 2a, its own DiTEngine), followed by ONE
+        AED_OP_SA_STEP_VARIANTS and one advance.  When a row's segment starts its x_t is xts[tstart] and its solver history
+        extra[tstart - 1]; a row with no history to take (tstart == T, first_order, a first-order scheduler) gets zeros
+        and coefficient table 1, whose first step is first order -- every other row reads table 0, second order from its
+        first step (models.py:1183-1184).
+
+        MAX_VARIANTS: a full-size DiT row (sequence 1025, width 1536) holds 11 activation buffers of the model width
+        (two residual streams, qkv = 3, attention output, cross-attention query, the gated FF = 4): 11 * 1025 * 1536 * 4 B
+        = 69 MB, and its per-prompt K/V of 24 blocks, 24 * 130 * 3072 * 4 B = 38 MB: 0.11 GB.  Every segment keeps its own
+        engine, so K variants with K distinct tstarts hold 2 * (1 + ... + K) = K * (K + 1) rows: 72 rows = 7.7 GB at
+        K = 8 and, with the max_plans = 4 cached loop shapes, 31 GB beside 4.2 GB of weights; K = 16 would be 272 rows =
+        29 GB per plan, 117 GB cached."""
+        s = self.sched
+        T = s.num_inference_steps
+        K = len(tstarts)
+        order, segs = variant_plan(tstarts, zs.shape[0], self.MAX_VARIANTS)
+        if len(cfg_tars) != K:
+            raise ValueError(f"edit_variants: {len(cfg_tars)} cfg_tar values for {K} variants")
+        tgt, neg = self._ctx_rows(ctx_tgt, K, "target"), self._ctx_rows(ctx_neg, K, "negative")
+        S = tgt[0].shape[1]
+        if any(c.shape[1] != S for c in tgt + neg):
+            raise ValueError(f"edit_variants: context lengths differ between rows ({sorted({c.shape[1] for c in tgt + neg})})")
+        ts = [int(tstarts[v]) for v in order]                      # sorted rows
+        if any(t > T for t in ts):
+            raise ValueError(f"edit_variants: tstart {max(ts)} beyond the {T} steps of the schedule")
+        seeded = not first_order and s.config.solver_order > 1     # models.py:1183-1184: history exists below T
+        no_hist = [not seeded or t == T for t in ts]
+        if extra is None and not all(no_hist):
+            raise ValueError("a second-order start (tstart < T) needs the inversion's extra_info (models.py:1182)")
+        Z0 = segs[0]["tstart"]
+        numel = self.C * self.Lz
+        key = ("variants", K, T, tuple(sg["tstart"] for sg in segs), tuple(sg["a"] for sg in segs), S, self.arith)
+        plan = self._get_plan(key)
+        if plan is None:
+            buf = lambda *shape: torch.zeros(shape, device=self.device, dtype=torch.float32)      # noqa: E731
+            plan = self._plans[key] = dict(cur=buf(K, self.Lz, self.C), hist=buf(K, self.Lz, self.C),
+                                           zs=buf(Z0, self.Lz, self.C), coef=buf(2, Z0, L.SA_COEF_STRIDE), tt=buf(Z0),
+                                           cfg=buf(K), ctab=torch.zeros(K, device=self.device, dtype=torch.int32), segs=[])
+            for sg in segs:
+                a = sg["a"]
+                eng = self._dit(2 * a, S, plan["tt"], 1, 2 * a)
+                pre, post = Tape(self.device), Tape(self.device)
+                for blk in range(2):        # c_in depends on the step only: one scaled copy of the a active rows per block
+                    pre.copy2d(plan["cur"], eng.x_in[blk * a:(blk + 1) * a], rows=1, cols=a * numel, ld_src=a * numel,
+                               ld_dst=a * numel, state=self.state, idx_off=0, idx_mul=0, idx_stride=0, coef=plan["coef"],
+                               c_mul=1, c_off=0, c_stride=L.SA_COEF_STRIDE, c_col=0, name="x_in<-c_in*x_t")
+                post.sa_step_variants(cur=plan["cur"], zs=plan["zs"], v=eng.v, cfg=plan["cfg"], coef=plan["coef"],
+                                      state=self.state, hist=plan["hist"], numel=numel, a=a, Z=Z0, steps=Z0, R=2,
+                                      ctab=plan["ctab"])
+                post.advance(self.state)
+                pre.finalize()
+                post.finalize()
+                plan["segs"].append(dict(eng=eng, pre=pre, post=post))
+        cur, hist = plan["cur"], plan["hist"]
+        # refilled on every call: the captured graphs hold the buffers, not their contents
+        plan["zs"].copy_(zs[:Z0])
+        lon = min(T - Z0, s.config.solver_order)                   # table 0 is edit()'s table of the longest row
+        tables = torch.stack([sa_coefficient_table(s, T - Z0, Z0, lon, first_order=first_order),
+                              sa_coefficient_table(s, T - Z0, Z0, 0, first_order=first_order)])
+        plan["coef"].copy_(tables)
+        plan["tt"].copy_(tables[0, :, 9])
+        plan["cfg"].copy_(torch.tensor([float(cfg_tars[v]) for v in order], dtype=torch.float32))
+        plan["ctab"].copy_(torch.tensor([int(n) for n in no_hist], dtype=torch.int32))
+        glob = glob.reshape(1, -1)
+        for sg, sp in zip(segs, plan["segs"]):
+            a = sg["a"]
+            sp["eng"].set_conditioning(torch.cat([neg[v] for v in order[:a]] + [tgt[v] for v in order[:a]], 0),
+                                       glob.expand(2 * a, -1))
+        self.state.zero_()
+        for sg, sp in zip(segs, plan["segs"]):
+            lo, hi = sg["join"]
+            cur[lo:hi].copy_(xts[sg["tstart"]].expand(hi - lo, -1, -1))
+            if no_hist[lo]:                                        # rows of one segment share their tstart
+                hist[lo:hi].zero_()
+            else:
+                hist[lo:hi].copy_(extra[sg["tstart"] - 1].expand(hi - lo, -1, -1))
+            eng, pre, post = sp["eng"], sp["pre"], sp["post"]
+
+            def body(eng=eng, pre=pre, post=post):
+                pre.run()
+                eng.tape.run()
+                post.run()
+            self._run_graph(body, sg["steps"], use_graph, sp)
+        return cur[variant_positions(order)]                       # advanced indexing: a copy, in the caller's order

@@ -69,8 +69,8 @@ def inversion_reverse_variants(model, xts, zs, variants, etas=1.0, chunk=None):
     `variants`.  More than EditEngine.MAX_VARIANTS (or `chunk`) variants run as several calls, sorted by tstart so that a
     call holds few distinct start steps."""
     if getattr(model, "kind", None) == "stable_audio":
-        raise NotImplementedError("inversion_reverse_variants: Stable Audio is not supported (its solver keeps per-edit "
-                                  "history and its DiT takes one prompt per call)")
+        raise NotImplementedError("inversion_reverse_variants: Stable Audio is not supported here (its solver keeps "
+                                  "per-edit history); use stable_audio_variants.inversion_reverse_variants_sa")
     variants = list(variants)
     if not variants:
         raise ValueError("inversion_reverse_variants: the list of variants is empty")

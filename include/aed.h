@@ -121,6 +121,15 @@ enum aed_opcode {
                                  normalised; directions sorted by len * sigma_t^2 / const, descending and stable; previous = unit,
                                  probe = unit * const; in_norm / in_corr rows and the snapshots of iterations 20, 30, ... are
                                  written from a device iteration counter.  k <= 8                                            */
+    AED_OP_SA_STEP_VARIANTS = 34, /* one reverse step of `a` Stable Audio edit variants of ONE inverted clip at the same loop
+                                 step: rows [0, a) of x_t [K][numel] and of the history hist [K][numel], v [a uncond | a cond],
+                                 a per-row scalar CFG (device float[a]), ONE shared noise table zs [Z][numel] (row Z - step - 1;
+                                 Z = 0: one explicit z; null: no noise term) and a device int[a] (null: all 0) naming each row's
+                                 table of coef [R][steps][AED_SA_COEF_STRIDE] (a row without history steps at order 1 while the
+                                 others step at order 2).  Row v is bit-identical to AED_OP_SA_STEP in mode 1 with cfg = cfg[v]
+                                 on its own coefficient row and history (StableAudioEditEngine.edit_variants).
+                                 slots: p0=x_t p1=zs p2=v p3=ctab p4=cfg p5=coef p6=state p7=out (null: in place) p8=hist;
+                                 i0,i1=numel lo/hi i2=a i3=Z i4=s_imm i5=steps i6=R i7=s_mul i8=s_off                        */
     AED_OP_COUNT
 };
 
@@ -308,6 +317,16 @@ int aed_sa_get_zs_from_xts(const float* xt, float* xtm1, const float* v_u, const
 int aed_sa_reverse_step_with_custom_noise(const float* xt, const float* v_u, const float* v_c, float cfg_scalar,
                                           const float* coef_host, float* hist, const float* z, float* prev_out,
                                           int64_t numel, void* stream);
+
+/* aed_sa_reverse_step_with_custom_noise for n_variants (at most 16) edits of one inverted clip at the same step, one
+ * launch: xt, hist and prev_out (may be xt itself) are [n_variants][numel], v is [n_variants uncond | n_variants cond][numel],
+ * cfg a DEVICE float[n_variants], z [numel] shared by every row or NULL.  coef_rows_host holds n_tables coefficient rows,
+ * [n_tables][AED_SA_COEF_STRIDE], and ctab_host (HOST int[n_variants], or NULL: every row takes row 0) names each row's.
+ * Row r is bit-identical to aed_sa_reverse_step_with_custom_noise(xt[r], v[r], v[n_variants + r], cfg[r],
+ * coef_rows_host + ctab_host[r] * AED_SA_COEF_STRIDE, hist[r], z, prev_out[r], numel, stream).                          */
+int aed_sa_reverse_step_variants(const float* xt, const float* v, const float* cfg, int n_variants,
+                                 const float* coef_rows_host, const int* ctab_host, int n_tables, float* hist,
+                                 const float* z, float* prev_out, int64_t numel, void* stream);
 
 #ifdef __cplusplus
 }
