@@ -326,6 +326,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(CGParams p) {
         // order per element (z ascending), so the two paths are bit-identical.
         const size_t q4 = total >> 2;
         const float4* ws4 = reinterpret_cast<const float4*>(p.ws);
+        // simple rows (the condition of cg_epilogue.h): output row = m, so the four columns of a thread are one run of a row --
+        // their operands are requested together and finished with store_out's operations in store_out's order (bit-identical),
+        // without its two divisions and its scatter per element.  Op flag 0x8000 keeps the per-element path.
+        const bool simple = p.o_mul == 1 && p.o_add == 0 && p.out_bs == p.rpb && p.o_len == p.rpb && p.accumulate == 0 &&
+                            !(p.diag & 1);
+        const bool has_rv = p.rowvec != nullptr && !p.ln_mode;
         for (size_t e4 = (size_t)blockIdx.x * 256 + threadIdx.x; e4 < q4; e4 += (size_t)gridDim.x * 256) {
             float4 v = ws4[e4];
 #pragma unroll 4
@@ -336,6 +342,28 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(CGParams p) {
             const size_t e = e4 << 2;
             const int m = (int)(e / p.N);
             const int n = (int)(e - (size_t)m * p.N);
+            if (simple) {
+                float o[4] = {v.x, v.y, v.z, v.w}, bi[4], rw[4], rs[4];
+                const float* rvp = has_rv ? p.rowvec + (size_t)(m / p.rpb) * p.ld_rv + n : nullptr;
+                const float* rsp = p.res ? p.res + (size_t)m * p.ldr + n : nullptr;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    bi[j] = p.bias ? p.bias[n + j] : 0.f;
+                    rw[j] = has_rv ? rvp[j] : 0.f;
+                    rs[j] = p.res ? rsp[j] : 0.f;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (p.bias) o[j] += bi[j];
+                    if (has_rv) o[j] += rw[j];
+                    if (p.res) o[j] += rs[j];
+                    o[j] = aed_apply_act(o[j], p.out_act, p.out_p);
+                }
+                float* dst = p.C + (size_t)m * p.ldc + n;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dst[j] = o[j];
+                continue;
+            }
             store_out(p, m, n, v.x);
             store_out(p, m, n + 1, v.y);
             store_out(p, m, n + 2, v.z);
