@@ -2,7 +2,8 @@
 //   AED_OP_SA_STEP      CFG + StableAudWrapper.get_zs_from_xts / reverse_step_with_custom_noise
 //                       (/root/reference/code/models.py:1209-1271, :1282-1329): SDE-DPM-Solver++ of order 1 / 2 with the
 //                       previous data prediction kept ON THE DEVICE (the scheduler's `model_outputs` history)
-//   AED_OP_SA_STEP_VARIANTS  the reverse step of AED_OP_SA_STEP for the rows of K edits of one inversion, one launch
+//   AED_OP_SA_STEP_VARIANTS  the reverse step of AED_OP_SA_STEP for the rows of K edits of one inversion (or, with a
+//                       per-row table index, of up to N inversions), one launch
 //   AED_OP_ROTARY       partial rotary embedding of q and k inside the fused qkv buffer (DiT self-attention)
 //   AED_OP_SNAKE        Snake1d activation of the Oobleck VAE: x + sin^2(a x) / (b + 1e-9), per channel
 //   AED_OP_GAUSS_SAMPLE mean + (softplus(scale) + 1e-4) * noise (OobleckDiagonalGaussianDistribution.sample, models.py:1132-1133)
@@ -150,6 +151,9 @@ extern "C" int aed_sa_reverse_step_with_custom_noise(const float* xt, const floa
 // history and takes its first step at order 1 while the others are at order 2 -- its own coefficient table, named by a
 // device int[a] into coef [R][steps][AED_SA_COEF_STRIDE].  The noise is shared: row Z - step - 1 of zs [Z][numel].  Row v
 // is sa_step_kernel in mode 1 on that row: the same sa_step_math on the same operands.
+// With a device int[a] `src` the rows are edits of up to N inversions (StableAudioEditEngine.edit_clips): zs is
+// [N][Z][numel] and row v reads row Z - step - 1 of table src[v].  The launcher cannot read src; its producer checks that
+// every entry lies in [0, N).
 // Grid: x walks element chunks, y is the row, so one row of the full-size latent (numel = 65536) and sixteen both put a
 // block on every CU.  16-byte accesses are used when every row start is 16-byte aligned (numel % 4 == 0 and aligned
 // bases) AND there are enough of them for a block per CU; otherwise 4-byte accesses, which at a = 1, numel = 65536 give
@@ -161,7 +165,8 @@ struct SAVarStep {
     const float* v;       // [2a][numel]
     const float* cfg;     // [a]
     float* hist;          // [K][numel]
-    const float* zs;      // [Z][numel] | one z (Z <= 0) | null
+    const float* zs;      // [Z][numel] | one z (Z <= 0) | null ; with src: [N][Z][numel]
+    const int* src;       // [a] noise table of every row (nullable: the one shared table)
     const float* coef;    // [R][steps][AED_SA_COEF_STRIDE]; null => the explicit form (c_row)
     const int* ctab;      // [a] coefficient table of every row (nullable: table 0)
     const int* state;     // device step counter (nullable -> s_imm)
@@ -184,6 +189,7 @@ __global__ __launch_bounds__(256) void sa_step_variants_kernel(SAVarStep p) {
     float* hist = p.hist + base;
     float* out = p.out + base;
     const float* z = !p.zs ? nullptr : (p.Z <= 0 ? p.zs : p.zs + (size_t)(p.Z - s - 1) * p.numel);
+    if (p.src) z += (size_t)p.src[row] * (size_t)p.Z * p.numel;       // launcher: src comes with a table, Z >= 1
     const size_t units = p.numel / VEC;                                // VEC == 4 only when numel % 4 == 0
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < units; e += (size_t)gridDim.x * 256) {
         if constexpr (VEC == 4) {
@@ -226,6 +232,8 @@ static int launch_sa_variants(const SAVarStep& p, hipStream_t s, const char* wha
 //        p5=coef [R][steps][AED_SA_COEF_STRIDE]  p6=state (nullable)  p7=out (null => in place into p0)  p8=hist [K][numel]
 //   i0,i1=numel lo/hi  i2=a  i3=Z  i4=s_imm  i5=steps (rows per coefficient table)  i6=R
 //   i7=s_mul i8=s_off (step = state*s_mul + s_off)
+//   p9=src int[a] (device; noise table of a row; null => ONE table, i9 unread)  i9=N: with src, zs is [N][Z][numel] and
+//   row v reads row Z - step - 1 of table src[v] (values in [0, N): checked by the host that fills src)
 int launch_sa_step_variants(const aed_op* op, hipStream_t s) {
     SAVarStep p = {};
     p.cur = (const float*)op->p[0]; p.zs = (const float*)op->p[1]; p.v = (const float*)op->p[2];
@@ -234,6 +242,11 @@ int launch_sa_step_variants(const aed_op* op, hipStream_t s) {
     p.numel = (size_t)(uint32_t)op->i[0] | ((size_t)(uint32_t)op->i[1] << 32);
     p.a = op->i[2]; p.Z = op->i[3]; p.s_imm = op->i[4]; p.steps = op->i[5];
     p.s_mul = op->i[7] > 0 ? op->i[7] : 1; p.s_off = op->i[8];
+    p.src = (const int*)op->p[9];
+    if (p.src) {
+        AED_REQUIRE(p.zs && p.Z > 0, "sa_step_variants: src needs the noise tables zs [N][Z][numel] (Z = %d)", p.Z);
+        AED_REQUIRE(op->i[9] >= 1, "sa_step_variants: src with %d noise tables", op->i[9]);
+    }
     AED_REQUIRE(p.coef && op->i[6] >= 1 && p.steps >= 1, "sa_step_variants: %d coefficient tables of %d rows", op->i[6],
                 p.steps);
     return launch_sa_variants(p, s, "sa_step_variants");

@@ -653,14 +653,14 @@ class StableAudWrapper(PipelineWrapper):
             out = self._projection(start_seconds=[float(start)], end_seconds=[float(end)])
         return out.seconds_start_hidden_states.to(self.device), out.seconds_end_hidden_states.to(self.device)
 
-    def assemble_context(self, encoder_hidden_states, encoder_attention_mask):
-        """The DiT's cross-attention input of unet_forward (models.py:1340-1343)."""
-        ctx = torch.cat([encoder_hidden_states.to(self.device), self.seconds_start_hidden_states,
-                         self.seconds_end_hidden_states], dim=1)
+    def assemble_context(self, encoder_hidden_states, encoder_attention_mask, seconds=None):
+        """The DiT's cross-attention input of unet_forward (models.py:1340-1343).  seconds: the (start, end) hidden states
+        of duration_conditioning instead of the ones setup_extra_inputs left on the wrapper."""
+        start, end = seconds if seconds is not None else (self.seconds_start_hidden_states, self.seconds_end_hidden_states)
+        ctx = torch.cat([encoder_hidden_states.to(self.device), start, end], dim=1)
         return torch.zeros_like(ctx) if encoder_attention_mask is None else ctx
 
-    def setup_extra_inputs(self, x: torch.Tensor, init_timestep: torch.Tensor, extra_info=None,
-                           audio_start_in_s: float = 0, audio_end_in_s: Optional[float] = None) -> None:
+    def _duration_window(self, audio_start_in_s, audio_end_in_s):
         c, v = self.model.transformer.config, self.model.vae
         max_len = c.sample_size * v.hop_length / v.config.sampling_rate
         if audio_end_in_s is None:
@@ -669,11 +669,23 @@ class StableAudWrapper(PipelineWrapper):
             raise ValueError(f"The total audio length requested ({audio_end_in_s - audio_start_in_s}s) is longer than "
                              f"the model maximum possible length ({max_len}). Make sure that "
                              f"'audio_end_in_s-audio_start_in_s<={max_len}'.")
+        return audio_start_in_s, audio_end_in_s
+
+    def duration_conditioning(self, audio_end_in_s: Optional[float] = None, audio_start_in_s: float = 0):
+        """What setup_extra_inputs derives from a clip's duration, without touching the wrapper's state: the seconds-start
+        and seconds-end hidden states [1, 1, Dc] and the global token [1, 1, Dg] (stable_audio_batch conditions every
+        clip of a batch on its own duration)."""
+        start, end = self._encode_duration(*self._duration_window(audio_start_in_s, audio_end_in_s))
+        return start, end, torch.cat([start, end], dim=2)
+
+    def setup_extra_inputs(self, x: torch.Tensor, init_timestep: torch.Tensor, extra_info=None,
+                           audio_start_in_s: float = 0, audio_end_in_s: Optional[float] = None) -> None:
+        v = self.model.vae
+        audio_start_in_s, audio_end_in_s = self._duration_window(audio_start_in_s, audio_end_in_s)
         self.waveform_start = int(audio_start_in_s * v.config.sampling_rate)
         self.waveform_end = int(audio_end_in_s * v.config.sampling_rate)
-        self.seconds_start_hidden_states, self.seconds_end_hidden_states = self._encode_duration(audio_start_in_s,
-                                                                                                  audio_end_in_s)
-        self.audio_duration_embeds = torch.cat([self.seconds_start_hidden_states, self.seconds_end_hidden_states], dim=2)
+        self.seconds_start_hidden_states, self.seconds_end_hidden_states, self.audio_duration_embeds = \
+            self.duration_conditioning(audio_end_in_s, audio_start_in_s)
         s = self.model.scheduler
         s._init_step_index(init_timestep)
         t_to_idx = {float(t): k for k, t in enumerate(s.timesteps)}

@@ -375,7 +375,8 @@ class OobleckDecoder(_OobleckBase):
 class StableAudioEditEngine(LoopPlumbing):
     """Device-resident inversion / edit loops of the Stable Audio wrapper for ONE clip and ONE prompt per pass (the
     reference's DiT call cannot take more: its global token is batch 1, models.py:1345-1349); edit_variants runs K such
-    edits of one inversion as rows of one loop (DiTEngine takes a context and a global token per row).
+    edits of one inversion as rows of one loop (DiTEngine takes a context and a global token per row), edit_clips K edits
+    of up to N inversions, every row on its own clip's trajectory, noise, history and duration.
 
     DiT batch rows per timestep: [uncond | cond] (cond dropped for an empty source prompt, inversion_utils.py:86).
     `mode="batched"` runs G timesteps per DiT call in the forward inversion -- legal for the same reason as in
@@ -568,7 +569,8 @@ class StableAudioEditEngine(LoopPlumbing):
         return cur.clone()
 
     # ------------------------------------------------------------------ K edits of one inversion
-    MAX_VARIANTS = 8        # rows per edit_variants call; stable_audio_variants.py chunks longer lists (see edit_variants)
+    MAX_VARIANTS = 8        # rows per edit_variants / edit_clips call; stable_audio_variants.py and stable_audio_batch.py
+    #                         chunk longer lists (see edit_variants)
 
     @staticmethod
     def _ctx_rows(ctx, K, what):
@@ -628,14 +630,35 @@ class StableAudioEditEngine(LoopPlumbing):
         if extra is None and not all(no_hist):
             raise ValueError("a second-order start (tstart < T) needs the inversion's extra_info (models.py:1182)")
         Z0 = segs[0]["tstart"]
+
+        def join(sg):
+            lo, hi = sg["join"]
+            m1 = None if no_hist[lo] else extra[sg["tstart"] - 1].expand(hi - lo, -1, -1)
+            return xts[sg["tstart"]].expand(hi - lo, -1, -1), m1
+        return self._variant_loop(("variants", K), order, segs, tgt, neg, [glob.reshape(1, -1)] * K, cfg_tars, no_hist,
+                                  first_order, fill_noise=lambda buf: buf.copy_(zs[:Z0]), join=join, use_graph=use_graph)
+
+    def _variant_loop(self, key_head, order, segs, tgt, neg, globs, cfg_tars, no_hist, first_order, fill_noise, join,
+                      use_graph, src=None, n_tables=None):
+        """The segmented loop of edit_variants and edit_clips over the K rows `order` sorts (variant_plan).  tgt / neg /
+        globs / cfg_tars / src are in the caller's order, no_hist in the sorted one.  fill_noise(buf) refills the noise
+        buffer: [Z0, L, C], or [n_tables, Z0, L, C] with `src` (the table of every row, values in [0, n_tables)).
+        join(segment) returns the x_t rows and the history rows (None: zeros) of the rows that start at that segment;
+        rows of one segment share their tstart, so they all have a history or none has."""
+        s = self.sched
+        T = s.num_inference_steps
+        K, S = len(order), tgt[0].shape[1]
+        Z0 = segs[0]["tstart"]
         numel = self.C * self.Lz
-        key = ("variants", K, T, tuple(sg["tstart"] for sg in segs), tuple(sg["a"] for sg in segs), S, self.arith)
+        key = (*key_head, T, tuple(sg["tstart"] for sg in segs), tuple(sg["a"] for sg in segs), S, self.arith)
         plan = self._get_plan(key)
         if plan is None:
             buf = lambda *shape: torch.zeros(shape, device=self.device, dtype=torch.float32)      # noqa: E731
+            ints = lambda n: torch.zeros(n, device=self.device, dtype=torch.int32)                # noqa: E731
             plan = self._plans[key] = dict(cur=buf(K, self.Lz, self.C), hist=buf(K, self.Lz, self.C),
-                                           zs=buf(Z0, self.Lz, self.C), coef=buf(2, Z0, L.SA_COEF_STRIDE), tt=buf(Z0),
-                                           cfg=buf(K), ctab=torch.zeros(K, device=self.device, dtype=torch.int32), segs=[])
+                                           zs=buf(*(() if src is None else (n_tables,)), Z0, self.Lz, self.C),
+                                           coef=buf(2, Z0, L.SA_COEF_STRIDE), tt=buf(Z0), cfg=buf(K), ctab=ints(K),
+                                           src=None if src is None else ints(K), segs=[])
             for sg in segs:
                 a = sg["a"]
                 eng = self._dit(2 * a, S, plan["tt"], 1, 2 * a)
@@ -646,14 +669,16 @@ class StableAudioEditEngine(LoopPlumbing):
                                c_mul=1, c_off=0, c_stride=L.SA_COEF_STRIDE, c_col=0, name="x_in<-c_in*x_t")
                 post.sa_step_variants(cur=plan["cur"], zs=plan["zs"], v=eng.v, cfg=plan["cfg"], coef=plan["coef"],
                                       state=self.state, hist=plan["hist"], numel=numel, a=a, Z=Z0, steps=Z0, R=2,
-                                      ctab=plan["ctab"])
+                                      ctab=plan["ctab"], src=plan["src"], n_tables=n_tables or 1)
                 post.advance(self.state)
                 pre.finalize()
                 post.finalize()
                 plan["segs"].append(dict(eng=eng, pre=pre, post=post))
         cur, hist = plan["cur"], plan["hist"]
         # refilled on every call: the captured graphs hold the buffers, not their contents
-        plan["zs"].copy_(zs[:Z0])
+        fill_noise(plan["zs"])
+        if src is not None:
+            plan["src"].copy_(torch.tensor([int(src[v]) for v in order], dtype=torch.int32))
         lon = min(T - Z0, s.config.solver_order)                   # table 0 is edit()'s table of the longest row
         tables = torch.stack([sa_coefficient_table(s, T - Z0, Z0, lon, first_order=first_order),
                               sa_coefficient_table(s, T - Z0, Z0, 0, first_order=first_order)])
@@ -661,19 +686,19 @@ class StableAudioEditEngine(LoopPlumbing):
         plan["tt"].copy_(tables[0, :, 9])
         plan["cfg"].copy_(torch.tensor([float(cfg_tars[v]) for v in order], dtype=torch.float32))
         plan["ctab"].copy_(torch.tensor([int(n) for n in no_hist], dtype=torch.int32))
-        glob = glob.reshape(1, -1)
         for sg, sp in zip(segs, plan["segs"]):
             a = sg["a"]
             sp["eng"].set_conditioning(torch.cat([neg[v] for v in order[:a]] + [tgt[v] for v in order[:a]], 0),
-                                       glob.expand(2 * a, -1))
+                                       torch.cat([globs[v] for v in order[:a]] * 2, 0))
         self.state.zero_()
         for sg, sp in zip(segs, plan["segs"]):
             lo, hi = sg["join"]
-            cur[lo:hi].copy_(xts[sg["tstart"]].expand(hi - lo, -1, -1))
-            if no_hist[lo]:                                        # rows of one segment share their tstart
+            x, m1 = join(sg)
+            cur[lo:hi].copy_(x)
+            if m1 is None:
                 hist[lo:hi].zero_()
             else:
-                hist[lo:hi].copy_(extra[sg["tstart"] - 1].expand(hi - lo, -1, -1))
+                hist[lo:hi].copy_(m1)
             eng, pre, post = sp["eng"], sp["pre"], sp["post"]
 
             def body(eng=eng, pre=pre, post=post):
@@ -682,3 +707,94 @@ class StableAudioEditEngine(LoopPlumbing):
                 post.run()
             self._run_graph(body, sg["steps"], use_graph, sp)
         return cur[variant_positions(order)]                       # advanced indexing: a copy, in the caller's order
+
+    # ------------------------------------------------------------------ K edits of up to N inversions
+    @torch.inference_mode()
+    def edit_clips(self, xts_list, zs_list, extra_list, rows, first_order=False, use_graph=True):
+        """K edits of up to N DIFFERENT inverted clips in one device-resident loop.  xts_list[c] [T+1, L, C], zs_list[c]
+        [Z_c, L, C] and extra_list[c] [T, L, C] or None are clip c's trajectory, noise maps and solver history
+        (channels-last, as invert() returns them; every Stable Audio latent has the one shape [sample_size, C]).  rows: a
+        list of (clip, tstart, ctx_tgt [1, S, Dc], ctx_neg [1, S, Dc], glob [1, Dg], cfg_tar); row k is
+        `edit(xts_list[clip], zs_list[clip], tstart, ctx_tgt, ctx_neg, glob, cfg_tar, extra=extra_list[clip],
+        first_order=first_order)`.  Returns the edited latents [K, L, C] in the caller's order.
+
+        The loop is edit_variants' (rows sorted by tstart, largest first; segments between the distinct tstarts at DiT
+        batch 2a, an engine per segment; MAX_VARIANTS rows), except that a row joins from its OWN clip's xts[tstart] and
+        extra[tstart - 1], carries its own global token (its clip's duration) next to its contexts, and the step reads
+        its own clip's noise table: zs [N, Z0, L, C] (Z0 = max tstart; clip c's first min(Z0, Z_c) maps, zeros behind
+        them, never read) with src[row] = clip.  The solver coefficients depend on the loop step only, so the two tables
+        of edit_variants serve every row."""
+        s = self.sched
+        T = s.num_inference_steps
+        rows = list(rows)
+        clips, tstarts, order, segs = sa_clip_plan(xts_list, zs_list, extra_list, rows, T, (self.Lz, self.C),
+                                                   self.MAX_VARIANTS)
+        K, N = len(rows), len(xts_list)
+        tgt, neg, globs = [r[2] for r in rows], [r[3] for r in rows], [r[4].reshape(1, -1) for r in rows]
+        if any(c.dim() != 3 or c.shape[0] != 1 for c in tgt + neg):
+            raise ValueError("edit_clips: every target / negative context is one [1, S, Dc] tensor")
+        S = tgt[0].shape[1]
+        if any(c.shape[1] != S for c in tgt + neg):
+            raise ValueError(f"edit_clips: context lengths differ between rows ({sorted({c.shape[1] for c in tgt + neg})})")
+        seeded = not first_order and s.config.solver_order > 1     # models.py:1183-1184: history exists below T
+        no_hist = [not seeded or tstarts[v] == T for v in order]
+        for i, v in enumerate(order):
+            if not no_hist[i] and extra_list[clips[v]] is None:
+                raise ValueError(f"edit_clips: row {v} is a second-order start (tstart {tstarts[v]} < T = {T}) on clip "
+                                 f"{clips[v]}, which has no extra (the inversion's extra_info, models.py:1182)")
+
+        def fill_noise(buf):
+            for c, z in enumerate(zs_list):
+                n = min(buf.shape[1], z.shape[0])
+                buf[c, :n].copy_(z[:n])
+                buf[c, n:].zero_()
+
+        def join(sg):
+            idx = order[sg["join"][0]:sg["join"][1]]
+            x = torch.stack([xts_list[clips[v]][tstarts[v]] for v in idx])
+            if no_hist[sg["join"][0]]:
+                return x, None
+            return x, torch.stack([extra_list[clips[v]][tstarts[v] - 1] for v in idx])
+        return self._variant_loop(("clips", K, N), order, segs, tgt, neg, globs, [r[5] for r in rows], no_hist,
+                                  first_order, fill_noise=fill_noise, join=join, use_graph=use_graph, src=clips,
+                                  n_tables=N)     # clips: validated in sa_clip_plan, all < N
+
+
+def sa_clip_plan(xts_list, zs_list, extra_list, rows, T, latent_shape, max_rows=None):
+    """The host plan of StableAudioEditEngine.edit_clips: checks the inverted clips and the rows (clip, tstart, ...) that
+    edit them, then returns (clips, tstarts, order, segments) with variant_plan's order and segments over the rows'
+    tstarts.  Refuses an empty list, more than `max_rows`, lists of different lengths, a clip that is not ONE inversion of
+    `latent_shape` (L, C) over T + 1 points, a clip index outside the lists and a tstart outside [1, Z_c] of its OWN
+    clip's noise maps."""
+    if not rows:
+        raise ValueError("edit_clips: the list of rows is empty")
+    if max_rows is not None and len(rows) > max_rows:
+        raise ValueError(f"edit_clips: {len(rows)} rows in one call, at most {max_rows} "
+                         f"(stable_audio_batch.inversion_reverse_clips_sa splits longer lists)")
+    N = len(xts_list)
+    if N < 1 or len(zs_list) != N or len(extra_list) != N:
+        raise ValueError(f"edit_clips: {N} trajectories, {len(zs_list)} noise tables and {len(extra_list)} histories (one "
+                         f"of each per clip, at least one; a history may be None)")
+    want = tuple(latent_shape)
+    for c, (x, z, e) in enumerate(zip(xts_list, zs_list, extra_list)):
+        if x.dim() != 3 or z.dim() != 3 or tuple(x.shape[1:]) != want or tuple(z.shape[1:]) != want:
+            raise ValueError(f"edit_clips: clip {c} has xts {tuple(x.shape)} / zs {tuple(z.shape)}; every clip must be ONE "
+                             f"inversion of latent shape [L, C] = {list(want)}")
+        if x.shape[0] != T + 1:
+            raise ValueError(f"edit_clips: clip {c} holds {x.shape[0]} trajectory points, the schedule has T + 1 = {T + 1} "
+                             f"(one schedule per call)")
+        if e is not None and tuple(e.shape) != (T, *want):
+            raise ValueError(f"edit_clips: clip {c} has extra {tuple(e.shape)}, expected [T, L, C] = {[T, *want]}")
+    clips, tstarts = [], []
+    for k, row in enumerate(rows):
+        c, t = int(row[0]), int(row[1])
+        if not 0 <= c < N:
+            raise ValueError(f"edit_clips: row {k} names clip {c}, outside [0, {N}) (the clips the lists hold)")
+        Zc = min(zs_list[c].shape[0], T)
+        if not 1 <= t <= Zc:
+            raise ValueError(f"edit_clips: row {k} has tstart {t} outside [1, {Zc}] (the number of noise maps clip {c} "
+                             f"holds)")
+        clips.append(c)
+        tstarts.append(t)
+    order, segs = variant_plan(tstarts, max(tstarts), max_rows)
+    return clips, tstarts, order, segs

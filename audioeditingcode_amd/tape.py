@@ -584,15 +584,17 @@ class Tape:
                   [xts, zs, v_u, v_c, coef, state, hist, out, extra], name=name, nbytes=4 * numel * 7)
 
     def sa_step_variants(self, *, cur, zs, v, cfg, coef, state, hist, numel, a, Z, steps, R=1, ctab=None, out=None,
-                         s_imm=0, s_mul=1, s_off=0, name="sa_step_variants"):
+                         s_imm=0, s_mul=1, s_off=0, src=None, n_tables=1, name="sa_step_variants"):
         """One reverse step of the `a` Stable Audio edit variants in rows [0, a) of cur [K, numel] and hist [K, numel]
         (AED_OP_SA_STEP_VARIANTS): v [a uncond | a cond], cfg a device float[>= a], zs the shared noise table [Z, numel]
         (None: no noise term; Z = 0: zs is one explicit z), ctab a device int32[>= a] naming each row's table of
-        coef [R, steps, SA_COEF_STRIDE] (None: table 0).  out=None steps cur in place."""
+        coef [R, steps, SA_COEF_STRIDE] (None: table 0).  out=None steps cur in place.  src (a device int32[>= a]) makes
+        the rows edits of up to n_tables inversions: zs is then [n_tables, Z, numel] and row v reads table src[v], which
+        the caller keeps inside [0, n_tables) (StableAudioEditEngine.edit_clips)."""
         self._add(L.OP_SA_STEP_VARIANTS, [numel & 0xFFFFFFFF, numel >> 32, a, Z if zs is not None else 0, s_imm, steps, R,
-                                          s_mul, s_off],
-                  [], [cur, zs, v, ctab, cfg, coef, state, out, hist], name=name,
-                  nbytes=4 * numel * (6 * a + int(zs is not None)))
+                                          s_mul, s_off, n_tables if src is not None else 0],
+                  [], [cur, zs, v, ctab, cfg, coef, state, out, hist, src], name=name,
+                  nbytes=4 * numel * (6 * a + int(zs is not None) * (1 if src is None else a)))
 
     def gauss_sample(self, moments, noise, out, *, rows, C, name="gauss_sample"):
         self._add(L.OP_GAUSS_SAMPLE, [rows & 0xFFFFFFFF, rows >> 32, C, moments.stride(-2)], [], [moments, noise, out],

@@ -127,9 +127,13 @@ enum aed_opcode {
                                  Z = 0: one explicit z; null: no noise term) and a device int[a] (null: all 0) naming each row's
                                  table of coef [R][steps][AED_SA_COEF_STRIDE] (a row without history steps at order 1 while the
                                  others step at order 2).  Row v is bit-identical to AED_OP_SA_STEP in mode 1 with cfg = cfg[v]
-                                 on its own coefficient row and history (StableAudioEditEngine.edit_variants).
-                                 slots: p0=x_t p1=zs p2=v p3=ctab p4=cfg p5=coef p6=state p7=out (null: in place) p8=hist;
-                                 i0,i1=numel lo/hi i2=a i3=Z i4=s_imm i5=steps i6=R i7=s_mul i8=s_off                        */
+                                 on its own coefficient row and history (StableAudioEditEngine.edit_variants).  With a device
+                                 int[a] `src` (slot p9) and N tables zs [N][Z][numel] (Z >= 1) the rows belong to up to N
+                                 inversions and row v reads row Z - step - 1 of table src[v], values in [0, N)
+                                 (StableAudioEditEngine.edit_clips); without src the op is unchanged.
+                                 slots: p0=x_t p1=zs p2=v p3=ctab p4=cfg p5=coef p6=state p7=out (null: in place) p8=hist
+                                 p9=src (null: one shared table); i0,i1=numel lo/hi i2=a i3=Z i4=s_imm i5=steps i6=R i7=s_mul
+                                 i8=s_off i9=N (read with src only)                                                          */
     AED_OP_COUNT
 };
 
