@@ -30,6 +30,9 @@ OP_NAMES = ["nop", "conv_gemm", "gn_stats", "gn_apply", "layernorm", "attention"
 OP_PC_PROBE, OP_PC_JACOBIAN, OP_PC_ORTHONORMALISE = 31, 32, 33
 # the multi-row Stable Audio solver step (csrc/stable_audio.hip); tape.sa_step_variants names its record itself
 OP_SA_STEP_VARIANTS = 34
+# the step of rows of P-prompt segment edits (csrc/elementwise.hip); tape.step_segments names its record itself
+OP_REVERSE_STEP_SEGMENTS = 35
+SEG_MAX_P = 8               # prompts per row AED_OP_REVERSE_STEP_SEGMENTS takes
 PC_TAB_STRIDE = 4           # floats per slot of the ops' table: sqrt(abar_t), c0, c1, sigma_t^2 / const
 PC_MAX_EV = 8               # directions AED_OP_PC_ORTHONORMALISE takes
 ACT_NONE, ACT_SILU, ACT_LEAKY, ACT_TANH, ACT_LOGCLAMP = range(5)

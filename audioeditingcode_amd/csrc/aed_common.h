@@ -45,6 +45,7 @@ int launch_reverse_step(const aed_op* op, hipStream_t s);
 int launch_reverse_step_variants(const aed_op* op, hipStream_t s);
 int launch_drift_step_variants(const aed_op* op, hipStream_t s);
 int launch_reverse_step_rows(const aed_op* op, hipStream_t s);
+int launch_reverse_step_segments(const aed_op* op, hipStream_t s);
 int launch_pc_probe(const aed_op* op, hipStream_t s);
 int launch_pc_jacobian(const aed_op* op, hipStream_t s);
 int launch_pc_orthonormalise(const aed_op* op, hipStream_t s);

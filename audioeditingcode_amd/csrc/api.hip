@@ -60,7 +60,7 @@ static launcher_t g_table[AED_OP_COUNT] = {
     launch_layout, launch_layout, launch_splitk_reduce, launch_gn_scale_shift, launch_gn_small, launch_xattn_fold,
     launch_rotary, launch_snake, launch_sa_step, launch_gauss_sample, launch_reverse_step_variants,
     launch_drift_step_variants, launch_reverse_step_rows, launch_pc_probe, launch_pc_jacobian, launch_pc_orthonormalise,
-    launch_sa_step_variants,
+    launch_sa_step_variants, launch_reverse_step_segments,
 };
 
 extern "C" {

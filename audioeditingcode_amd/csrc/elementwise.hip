@@ -621,6 +621,131 @@ int launch_drift_step_variants(const aed_op* op, hipStream_t s) {
     return launch_drift(q, s, "drift_step_variants");
 }
 
+// ------------------------------------------------------------------------------------ K1 for rows of P-prompt segment edits
+// One reverse step of `a` rows, each a P-prompt segment edit of ONE inverted clip (EditEngine.edit_segments), all at the
+// same loop step: the U-Net's eps is [a uncond | P blocks of a cond] x numel, row v combines its P conditional rows with
+// its own blurred per-element guidance tensors cfg[v][p] (cfg_combine's tensor form: the first term assigned, later terms
+// added in ascending p), steps with the shared reverse_update and the ONE shared noise table, and then -- while a segment
+// of the row has not joined yet, lag[v][p] > step -- pulls x_{t-1} back to the recorded trajectory with the reference's
+// blend (inversion_utils.py:308-315) in its fp32 expression order:
+//   prev = sum_p mask[v][p] * (prev * (1 - af_p) + af_p * traj[Z - step - 1]),   af_p = alpha[v] where lag[v][p] > step, else 0
+// summed in ascending p.  Whether any prompt of a row lags is uniform across the wave: a branch, and a row in which none
+// does stores the plain step (NOT times the mask sum; the reference skips the blend, `apply_fix.any()`), bit-identical to
+// reverse_step_kernel with the row's cfg tensor.  lag = Z - tstart makes one trajectory row, Z - step - 1, serve every
+// row whatever its own largest tstart.  Grid-stride loop over element positions; a thread walks the rows in groups of 2
+// whose loads (x_t, 1 + P eps, P cfg, and P masks for a row that blends) are all issued before the group's first store.
+#define AED_SEG_MAX_P 8
+#define AED_SEG_MAX_ROWS 16
+struct SegmentStepParams {
+    VariantStepParams v;   // out == cur; eps: [a * (1 + P)][numel]; cfg: [K][P][numel]; zs / Z as in VariantStepParams
+    const float* mask;     // [K][P][numel]
+    const float* traj;     // [Z][numel] device-indexed, or one explicit row (Z == 0)
+    const int* lag;        // [K][P]
+    const float* alpha;    // [K]
+};
+
+template <int P>           // prompts per row: the per-row values stay in registers under constant indices (no scratch)
+__global__ __launch_bounds__(256) void reverse_step_segments_kernel(SegmentStepParams q) {
+    const VariantStepParams& p = q.v;
+    const int s = p.state ? p.state[0] * p.s_mul + p.s_off : p.s_imm;
+    float c0, c1, c2, c3, c4;
+    if (p.coef) { const float* c = p.coef + (size_t)s * AED_COEF_STRIDE; c0 = c[0]; c1 = c[1]; c2 = c[2]; c3 = c[3]; c4 = c[4]; }
+    else { c0 = p.c[0]; c1 = p.c[1]; c2 = p.c[2]; c3 = p.c[3]; c4 = p.c[4]; }
+    const size_t trow = p.Z > 0 ? (size_t)(p.Z - s - 1) * p.numel : 0;
+    const float* z = p.zs ? p.zs + trow : nullptr;
+    const float* traj = q.traj + trow;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < p.numel; e += (size_t)gridDim.x * 256) {
+        const float zz = z ? z[e] : 0.f;
+        const float tr = traj[e];
+        for (int v0 = 0; v0 < p.a; v0 += 2) {                         // 2 rows' loads issued before the first store
+            float x[2], u[2], c[2][P], g[2][P], m[2][P];
+            unsigned lags[2];                                         // bit j: prompt j of the row has not joined
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int v = v0 + r;
+                if (v >= p.a) break;
+                lags[r] = 0;
+#pragma unroll
+                for (int j = 0; j < P; ++j)
+                    if (q.lag[v * P + j] > s) lags[r] |= 1u << j;
+                x[r] = p.cur[(size_t)v * p.numel + e];
+                u[r] = p.eps[(size_t)v * p.numel + e];
+#pragma unroll
+                for (int j = 0; j < P; ++j) {
+                    c[r][j] = p.eps[((size_t)p.a * (1 + j) + v) * p.numel + e];
+                    g[r][j] = p.cfg[((size_t)v * P + j) * p.numel + e];
+                    if (lags[r]) m[r][j] = q.mask[((size_t)v * P + j) * p.numel + e];
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int v = v0 + r;
+                if (v >= p.a) break;
+                float acc = g[r][0] * (c[r][0] - u[r]);               // cfg_combine, tensor form: first term assigned,
+#pragma unroll
+                for (int j = 1; j < P; ++j) acc = acc + g[r][j] * (c[r][j] - u[r]);     // later terms added in ascending p
+                const float eps = u[r] + acc;
+                float prev;                                           // two calls: &zz must not meet null in a select
+                if (z) prev = reverse_update(x[r], eps, &zz, 0, p.v_pred, c0, c1, c2, c3, c4);
+                else prev = reverse_update(x[r], eps, nullptr, 0, p.v_pred, c0, c1, c2, c3, c4);
+                if (lags[r]) {                                        // inversion_utils.py:308-315
+                    const float al = q.alpha[v];
+                    float sum = 0.f;
+#pragma unroll
+                    for (int j = 0; j < P; ++j) {
+                        const float af = ((lags[r] >> j) & 1u) ? al : 0.f;
+                        const float term = m[r][j] * (prev * (1.f - af) + af * tr);
+                        sum = (j == 0) ? term : sum + term;
+                    }
+                    prev = sum;
+                }
+                p.out[(size_t)v * p.numel + e] = prev;
+            }
+        }
+    }
+}
+
+// slots: p0=cur [K][numel] (rows [0, a) stepped IN PLACE)  p1=zs base | z | null (no noise)  p2=eps [a(1+P)][numel]:
+//        [a uncond | P blocks of a cond], prompt j of row v is row a + j*a + v  p3=lag int[K][P] (device; Z - tstart)
+//        p4=cfg [K][P][numel]  p5=coef table (nullable)  p6=state (nullable)  p7=mask [K][P][numel]
+//        p8=alpha float[K] (device; fix_alpha per row)  p9=traj [Z][numel] | one row (the recorded trajectory xts[0:Z])
+//   i0,i1=numel lo/hi  i2=a (1..16)  i3=Z (rows of p1 and p9, both read at Z - step - 1; 0 => p1 and p9 are explicit rows,
+//   without p6 only)  i4=s_imm  i5=v_pred  i6=has_noise  i7=s_mul i8=s_off (step = state*s_mul + s_off)  i9=P (1..8)
+//   f1..f5 = c0..c4 immediates (used when p5 is null)
+int launch_reverse_step_segments(const aed_op* op, hipStream_t s) {
+    SegmentStepParams q = {};
+    VariantStepParams& p = q.v;
+    p.cur = (const float*)op->p[0]; p.out = (float*)op->p[0];
+    p.zs = op->i[6] ? (const float*)op->p[1] : nullptr;
+    p.eps = (const float*)op->p[2]; p.cfg = (const float*)op->p[4];
+    p.coef = (const float*)op->p[5]; p.state = (const int*)op->p[6];
+    p.numel = (size_t)(uint32_t)op->i[0] | ((size_t)(uint32_t)op->i[1] << 32);
+    p.a = op->i[2]; p.Z = op->i[3]; p.s_imm = op->i[4]; p.v_pred = op->i[5];
+    p.s_mul = op->i[7] > 0 ? op->i[7] : 1; p.s_off = op->i[8];
+    for (int k = 0; k < 5; ++k) p.c[k] = op->f[1 + k];
+    q.lag = (const int*)op->p[3]; q.mask = (const float*)op->p[7];
+    q.alpha = (const float*)op->p[8]; q.traj = (const float*)op->p[9];
+    const int P = op->i[9];
+    AED_REQUIRE(!op->i[6] || op->p[1], "reverse_step_segments: noise requested but zs is null");
+    AED_REQUIRE(p.cur && p.eps && p.cfg && q.lag && q.mask && q.alpha && q.traj,
+                "reverse_step_segments: null pointer (cur, eps, lag, cfg, mask, alpha or traj)");
+    AED_REQUIRE(P >= 1 && P <= AED_SEG_MAX_P, "reverse_step_segments: P %d outside [1, %d]", P, AED_SEG_MAX_P);
+    AED_REQUIRE(p.a >= 1 && p.a <= AED_SEG_MAX_ROWS, "reverse_step_segments: a %d outside [1, %d]", p.a, AED_SEG_MAX_ROWS);
+    AED_REQUIRE(p.Z >= (p.state ? 1 : 0), "reverse_step_segments: Z %d, the device counter indexes tables of Z >= 1 rows", p.Z);
+    AED_REQUIRE(p.state || p.Z == 0 || (p.s_imm >= 0 && p.s_imm < p.Z), "reverse_step_segments: step %d outside [0, Z = %d)",
+                p.s_imm, p.Z);
+    if (p.numel == 0) return 0;
+    const dim3 grid(grid_for(p.numel));
+    switch (P) {
+#define AED_SEG_CASE(n) case n: hipLaunchKernelGGL(reverse_step_segments_kernel<n>, grid, dim3(256), 0, s, q); break;
+        AED_SEG_CASE(1) AED_SEG_CASE(2) AED_SEG_CASE(3) AED_SEG_CASE(4) AED_SEG_CASE(5) AED_SEG_CASE(6) AED_SEG_CASE(7)
+        AED_SEG_CASE(8)
+#undef AED_SEG_CASE
+    }
+    AED_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // slots (both): p0=xts base | xt   p1=zs base | z   p2=eps_u  p3=eps_c  p4=cfg  p5=coef table  p6=state  p7=out
 //   i0,i1=numel lo/hi  i2=P  i3=T (invert: #steps; reverse: #zs, 0 => p1 is the explicit z)  i4=s_imm
 //   i5=v_pred  i6=numerical_fix | has_noise   i7=s_mul i8=s_off (step = state*s_mul + s_off; timestep-batched loops)

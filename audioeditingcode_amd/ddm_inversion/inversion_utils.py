@@ -5,7 +5,8 @@ Two execution paths, both entirely on HIP kernels:
   * fast path (default): the device-resident hipGraph loops of editing.EditEngine;
   * hook path: when the caller asks for h-space / skip-connection taps or replacements, or prompts
     have unequal `tstart` (multi-prompt trajectory blend), the loop is driven step by step through the
-    wrapper's own methods exactly like the reference does.
+    wrapper's own methods exactly like the reference does.  inversion_reverse_process(segment_loop="device") runs the
+    unequal-`tstart` case on the device loop instead (segments.py, EditEngine.edit_segments).
 """
 from typing import Dict, List, Optional, Tuple, Union
 
@@ -175,7 +176,13 @@ def inversion_reverse_process(model, xT: torch.Tensor, tstart: torch.Tensor, fix
                               skipconns_replace: Optional[Dict[int, torch.Tensor]] = None,
                               zero_out_resconns: Optional[Union[int, List]] = None, extract_h_space: bool = False,
                               extract_skipconns: bool = False, duration: Optional[float] = None,
-                              first_order: bool = False, extra_info: Optional[List] = None) -> Tuple:
+                              first_order: bool = False, extra_info: Optional[List] = None,
+                              segment_loop: str = "host") -> Tuple:
+    """segment_loop: where a multi-prompt edit with UNEQUAL tstart runs -- "host" (default): step by step through the
+    wrapper's methods, like the reference; "device": as one row of the device-resident segments loop
+    (segments.inversion_reverse_segments).  Every other call is routed as before."""
+    if segment_loop not in ("host", "device"):
+        raise ValueError(f"segment_loop {segment_loop!r}: expected \"host\" or \"device\"")
     batch_size = len(prompts)
     tstart = torch.as_tensor(tstart).reshape(-1).cpu()
     if getattr(model, "kind", None) == "stable_audio":
@@ -200,6 +207,17 @@ def inversion_reverse_process(model, xT: torch.Tensor, tstart: torch.Tensor, fix
         # a list that switches the noise term off at SOME steps: the reference skips `+ eta*sigma*z` there (models.py:152),
         # the fused kernel would multiply a possibly non-finite z by zero -- take the literal path
         general = general or (any(e == 0 for e in used) and any(e > 0 for e in used))
+    if segment_loop == "device" and uneven:
+        why = "h-space / skip-connection hooks" if hooks else \
+            "a start index that differs from the number of noise maps, or an eta list that is zero at some steps" if general \
+            else None
+        if why:
+            raise ValueError(f"segment_loop=\"device\": the device loop does not run {why}; use segment_loop=\"host\"")
+        from ..segments import inversion_reverse_segments
+        w = inversion_reverse_segments(model, xT, zs, [dict(
+            prompts=list(prompts), neg_prompts=list(neg_prompts), tstart=[int(t) for t in tstart],
+            cfg_scales=list(cfg_scales), cutoff_points=cutoff_points, fix_alpha=fix_alpha)], eta=list(etas))
+        return w, zs
     if hooks or uneven or general:
         return _reverse_with_hooks(model, xT, tstart, fix_alpha, etas, prompts, neg_prompts, cfg_scales, zs,
                                    cutoff_points, hspace_add, hspace_replace, skipconns_replace, zero_out_resconns,

@@ -142,6 +142,48 @@ def _variant_rows(cond, K, what):
     raise ValueError(f"edit_variants: {what} has {cond.rows} rows for {K} variants")
 
 
+SEGMENT_KINDS = ("audioldm", "audioldm2", "tango")
+MAX_SEGMENT_BATCH = 32   # U-Net rows, a * (1 + P), of one edit_segments call
+
+
+def segments_plan(rows, n_zs, kind, latent_shape=None):
+    """The host plan of EditEngine.edit_segments.  rows: (tstarts[P], cond_tgt, cond_neg, cfg_tensor [P, C, H, W],
+    masks [P, C, H, W], fix_alpha); n_zs: the noise maps the caller holds; kind: the engine's.  Returns dict(P, tstarts:
+    per row its P ints, order, segs: variant_plan's over the rows' LARGEST tstart -- a row joins the loop where its first
+    segment starts).  Refuses an engine kind other than AudioLDM / AudioLDM2 / TANGO, an empty list, rows with differing
+    P, P outside [1, 8], more than 32 U-Net rows a * (1 + P), a tstart outside [1, n_zs], conditioning that is not P
+    target rows and one negative row, and (with `latent_shape` = (H, W, C)) tensors of another shape."""
+    if kind not in SEGMENT_KINDS:
+        raise ValueError(f"edit_segments: engine kind {kind!r} is not supported (AudioLDM, AudioLDM2, TANGO)")
+    rows = list(rows)
+    if not rows:
+        raise ValueError("edit_segments: the list of rows is empty")
+    tstarts = [[int(t) for t in row[0]] for row in rows]
+    P = len(tstarts[0])
+    if any(len(ts) != P for ts in tstarts):
+        raise ValueError(f"edit_segments: rows with {sorted({len(ts) for ts in tstarts})} prompts in one call (all rows of a "
+                         f"call share P)")
+    if not 1 <= P <= L.SEG_MAX_P:
+        raise ValueError(f"edit_segments: {P} prompts per row, the segments step takes 1 to {L.SEG_MAX_P}")
+    if len(rows) * (1 + P) > MAX_SEGMENT_BATCH:
+        raise ValueError(f"edit_segments: {len(rows)} rows of {P} prompts are {len(rows) * (1 + P)} U-Net rows, at most "
+                         f"{MAX_SEGMENT_BATCH} (segments.inversion_reverse_segments splits longer lists)")
+    want = None if latent_shape is None else (P, latent_shape[2], latent_shape[0], latent_shape[1])
+    for k, (row, ts) in enumerate(zip(rows, tstarts)):
+        for t in ts:
+            if not 1 <= t <= n_zs:
+                raise ValueError(f"edit_segments: row {k} has tstart {t} outside [1, {n_zs}] (the number of noise maps zs "
+                                 f"holds)")
+        if row[1].rows != P or row[2].rows != 1:
+            raise ValueError(f"edit_segments: row {k} has {row[1].rows} target and {row[2].rows} negative conditioning rows, "
+                             f"expected {P} and 1")
+        if want is not None and (tuple(row[3].shape) != want or tuple(row[4].shape) != want):
+            raise ValueError(f"edit_segments: row {k} has a cfg tensor {tuple(row[3].shape)} and masks {tuple(row[4].shape)}, "
+                             f"expected [P, C, H, W] = {list(want)}")
+    order, segs = variant_plan([max(ts) for ts in tstarts], n_zs)
+    return dict(P=P, tstarts=tstarts, order=order, segs=segs)
+
+
 def clip_plan(xts_list, zs_list, rows, T, latent_shape, max_rows=None):
     """The host plan of EditEngine.edit_clips: checks the inverted clips and the rows (clip, tstart, ...) that edit them,
     then returns (clips, tstarts, order, segments) with variant_plan's order and segments over the rows' tstarts.  Refuses
@@ -796,13 +838,16 @@ class EditEngine(LoopPlumbing):
     MAX_VARIANTS = 16       # rows per edit_variants / edit_clips call (U-Net batch <= 32); variants.py and batch.py chunk
 
     def _variant_loop(self, tag, order, segs, tgt, neg, cfgs, eta, noise_ok, fill_noise, join_rows, use_graph, src=None,
-                      n_tables=0, drift=None, n_steps=None, rowsel=None):
+                      n_tables=0, drift=None, n_steps=None, rowsel=None, seg=None):
         """The segmented loop of edit_variants and edit_clips.  order / segs: variant_plan's; tgt / neg / cfgs: per row in
         the caller's order; fill_noise(buf) loads the plan's noise buffer, join_rows(seg) returns the x_t rows that start
         at a segment from (segment, the loop's row buffer).  src (the table of every row, caller's order) with n_tables makes
         the noise buffer [n_tables, Z0, H, W, C] and the step op read table src[row]; without it the one table
         [Z0, H, W, C] is shared.  drift (drift_variants: dict(vecs [S, n_ev, H, W, C], w [S, K, n_ev] in the caller's row
-        order, s_first, shift_np, mask, fix_alpha, par, fix_mode)) makes the step op the PC drift step.  n_steps stops the
+        order, s_first, shift_np, mask, fix_alpha, par, fix_mode)) makes the step op the PC drift step.  seg
+        (edit_segments: dict(P, cfg and mask [K, P, C, H, W], lag [K, P], alpha [K] in the caller's row order, traj
+        [Z0, H, W, C])) makes every row a P-prompt segment edit: tgt[v] holds P rows, a segment's U-Net batch is
+        [a uncond | P blocks of a cond] and the step op the segments step.  n_steps stops the
         loop after that many steps.  Returns the rows [K, H, W, C] in the caller's order."""
         s = self.sched
         T = s.num_inference_steps
@@ -812,7 +857,10 @@ class EditEngine(LoopPlumbing):
         has_noise = int(variant_noise(eta_rows) and noise_ok)
         numel = self.C * self.H * self.W
         v_pred = int(s.config.prediction_type == "v_prediction")
-        groups_all = [neg[v] for v in order] + [tgt[v] for v in order]
+        P = 1 if seg is None else seg["P"]
+        B = 1 + P                                   # U-Net rows per loop row: [a uncond | P blocks of a cond]
+        groups_all = [neg[v] for v in order] + ([tgt[v] for v in order] if seg is None else
+                                                [tgt[v].select([j]) for j in range(P) for v in order])
         L0, L1 = self._ctx_lens(groups_all)
         tables = () if src is None else (n_tables,)
         R = None if rowsel is None else len(rowsel["coefs"])
@@ -823,7 +871,7 @@ class EditEngine(LoopPlumbing):
                                           drift["fix_mode"], float(drift["fix_alpha"]))
         key = (tag, K, *(tables if rowsel is None else ()), T, tuple(sg["tstart"] for sg in segs),
                tuple(sg["a"] for sg in segs), L0, L1, v_pred, has_noise,
-               tuple(self._arith_for(2 * sg["a"]) for sg in segs), *dkey, *rkey)
+               tuple(self._arith_for(B * sg["a"]) for sg in segs), *dkey, *rkey, *(() if seg is None else (P,)))
         plan = self._get_plan(key)
         if plan is None:
             plan = self._plans[key] = dict(
@@ -841,16 +889,26 @@ class EditEngine(LoopPlumbing):
                 plan.update(vecs=dev_buf(S, n_ev, self.H, self.W, self.C), w=dev_buf(S, K, n_ev),
                             mask=dev_buf(self.H, self.W, self.C) if drift["fix_mode"] else None,
                             par=dev_buf(T + 1, self.H, self.W, self.C) if drift["fix_mode"] == 1 else None)
+            if seg is not None:         # per row and prompt: guidance tensor, segment mask and lag; per row: fix_alpha
+                lat = (self.H, self.W, self.C)
+                plan.update(cfg=torch.zeros((K, P, *lat), device=self.device, dtype=torch.float32),
+                            mask=torch.zeros((K, P, *lat), device=self.device, dtype=torch.float32),
+                            lag=torch.zeros((K, P), device=self.device, dtype=torch.int32),
+                            alpha=torch.zeros(K, device=self.device, dtype=torch.float32),
+                            traj=torch.zeros((Z0, *lat), device=self.device, dtype=torch.float32))
             for sg in segs:
                 a = sg["a"]
-                eng = self.unet(2 * a, L0, L1, share=1)
+                eng = self.unet(B * a, L0, L1, share=1)
                 pre, post = Tape(self.device), Tape(self.device)
-                for blk in range(2):
+                for blk in range(B):
                     pre.copy2d(plan["cur"], eng.x_in[blk * a:(blk + 1) * a], rows=1, cols=a * numel, ld_src=a * numel,
                                ld_dst=a * numel, name="x_in<-x_t")
-                step = dict(cur=plan["cur"], zs=plan["zs"] if has_noise else None, eps=eng.eps[:2 * a], cfg=plan["cfg"],
+                step = dict(cur=plan["cur"], zs=plan["zs"] if has_noise else None, eps=eng.eps[:B * a], cfg=plan["cfg"],
                             coef=plan["coef"], state=plan["state"], numel=numel, a=a, Z=Z0, v_pred=v_pred)
-                if rowsel is not None:
+                if seg is not None:
+                    post.step_segments(**step, mask=plan["mask"], lag=plan["lag"], alpha=plan["alpha"], traj=plan["traj"],
+                                       P=P)
+                elif rowsel is not None:
                     post.step_rows(**step, ztab=plan["rowsel"][0], ctab=plan["rowsel"][1], N=tables[0], R=R, steps=Z0)
                 elif drift is None:
                     post.step_variants(**step, src=plan["src"], N=n_tables)
@@ -874,7 +932,15 @@ class EditEngine(LoopPlumbing):
                                             for k in rowsel["coefs"]]))
             plan["rowsel"].copy_(torch.tensor([[rowsel["ztab"][v] if has_noise else -1 for v in order],
                                                [rowsel["ctab"][v] for v in order]], dtype=torch.int32))
-        plan["cfg"].copy_(torch.tensor([float(cfgs[v]) for v in order], dtype=torch.float32))
+        if seg is None:
+            plan["cfg"].copy_(torch.tensor([float(cfgs[v]) for v in order], dtype=torch.float32))
+        else:       # data, not part of the captured shape: other tstarts of the same maxima replay the same graphs
+            rows = list(order)
+            self.to_nhwc(seg["cfg"][rows], out=plan["cfg"])
+            self.to_nhwc(seg["mask"][rows], out=plan["mask"])
+            plan["lag"].copy_(seg["lag"][rows])
+            plan["alpha"].copy_(seg["alpha"][rows])
+            plan["traj"].copy_(seg["traj"])
         if src is not None:
             plan["src"].copy_(torch.tensor([src[v] for v in order], dtype=torch.int32))
         if drift is not None:
@@ -887,8 +953,8 @@ class EditEngine(LoopPlumbing):
         self._upload_timesteps(s.timesteps, T)
         for sg, sp in zip(segs, plan["segs"]):
             a = sg["a"]
-            self._set_cond(sp["eng"], groups_all[:a] + groups_all[K:K + a])
-            self._patch_time(sp["eng"], self.ts_dev, 1, 2 * a, offset=T - Z0, state=plan["state"])
+            self._set_cond(sp["eng"], [g for blk in range(B) for g in groups_all[blk * K:blk * K + a]])
+            self._patch_time(sp["eng"], self.ts_dev, 1, B * a, offset=T - Z0, state=plan["state"])
         plan["state"].zero_()
         left = None if n_steps is None else max(0, int(n_steps))
         for sg, sp in zip(segs, plan["segs"]):
@@ -934,6 +1000,38 @@ class EditEngine(LoopPlumbing):
             fill_noise=lambda buf: buf.copy_(zs[:buf.shape[0], 0]),
             join_rows=lambda sg, cur: xts[sg["tstart"], 0].expand(sg["join"][1] - sg["join"][0], -1, -1, -1),
             use_graph=use_graph)
+
+    # ------------------------------------------------------------------ K segment edits of one inversion
+    @torch.inference_mode()
+    def edit_segments(self, xts, zs, rows, eta=1.0, use_graph=True, n_steps=None):
+        """K multi-prompt segment edits of ONE inverted clip in one device-resident loop (the reference's localised edit,
+        inversion_utils.py:177-200 and :308-315: prompt p edits its segment of the clip from its own tstart, and until a
+        later-starting segment has joined the sample is pulled back to the recorded trajectory with fix_alpha).  xts
+        [T+1, 1, H, W, C] and zs [>= max tstart, 1, H, W, C] are channels-last, as invert() returns them.  rows: a list of
+        (tstarts[P], cond_tgt: P rows, cond_neg: one row, cfg_tensor [P, C, H, W], masks [P, C, H, W], fix_alpha), the two
+        tensors as _segment_tensors builds them; all rows of a call share P.  Row k is inversion_reverse_process with
+        these tstarts on xts and zs[:max(tstarts)].  eta: one float, or the reference's per-step list shared by every row.
+
+        The loop is edit_variants' over the rows' LARGEST tstart (sorted, largest first; segments between the distinct
+        maxima; a row is set to xts[max tstart] when its segment starts) at U-Net batch a * (1 + P), with the segments
+        step (AED_OP_REVERSE_STEP_SEGMENTS).  The tstarts below a row's maximum, fix_alpha, the cfg and mask tensors, the
+        noise and the trajectory are plan buffers refilled on every call: a call with other tstarts of the same maxima
+        replays the same graphs.  n_steps stops after that many loop steps.
+        Returns the edited latents [K, H, W, C] in the caller's order."""
+        if xts.dim() != 5 or xts.shape[1] != 1:
+            raise ValueError(f"edit_segments edits ONE inverted clip; xts is {tuple(xts.shape)}, expected [T+1, 1, H, W, C]")
+        rows = list(rows)
+        n_zs = self.sched.num_inference_steps if zs is None else zs.shape[0]
+        plan = segments_plan(rows, n_zs, self.kind, (self.H, self.W, self.C))
+        Z0 = plan["segs"][0]["tstart"]
+        seg = dict(P=plan["P"], cfg=torch.stack([r[3] for r in rows]), mask=torch.stack([r[4] for r in rows]),
+                   lag=Z0 - torch.tensor(plan["tstarts"], dtype=torch.int32),
+                   alpha=torch.tensor([float(r[5]) for r in rows], dtype=torch.float32), traj=xts[:Z0, 0])
+        return self._variant_loop(
+            "segments", plan["order"], plan["segs"], [r[1] for r in rows], [r[2] for r in rows], None, eta, zs is not None,
+            fill_noise=lambda buf: buf.copy_(zs[:buf.shape[0], 0]),
+            join_rows=lambda sg, cur: xts[sg["tstart"], 0].expand(sg["join"][1] - sg["join"][0], -1, -1, -1),
+            use_graph=use_graph, n_steps=n_steps, seg=seg)
 
     # ------------------------------------------------------------------ edits of many inversions
     @torch.inference_mode()

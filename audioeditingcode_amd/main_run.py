@@ -18,10 +18,11 @@ from .utils import load_audio, resampler_label, set_reproducability, synthetic_c
 
 def edit_clip(ldm_stable, x0, source_prompt, target_prompt, target_neg_prompt, cfg_src, cfg_tar, T, tstart,
               mode="ours", eta=1.0, schedule="sequential", timestep_group=8, cutoff_points=None, fix_alpha=0.1,
-              duration=None):
+              duration=None, segment_loop="host"):
     """main_run.py:104-185 for one mel `x0` [1,1,T_mel,64] (Stable Audio: one waveform [channels, n]): returns (edited
     waveform, original-vocoded waveform, edited latent).  `tstart`: int or one value per target prompt
-    (main_run.py:104-110)."""
+    (main_run.py:104-110).  `segment_loop`: "host" | "device", where an edit with unequal per-prompt tstart runs
+    (inversion_reverse_process)."""
     tstart = [int(tstart)] if isinstance(tstart, (int, float)) else [int(t) for t in tstart]
     if len(tstart) != len(target_prompt):
         if len(tstart) == 1:
@@ -55,7 +56,7 @@ def edit_clip(ldm_stable, x0, source_prompt, target_prompt, target_neg_prompt, c
                                                   prompts=target_prompt, neg_prompts=target_neg_prompt,
                                                   cfg_scales=cfg_tar, zs=zs[:int(T - min(skip))],
                                                   cutoff_points=cutoff_points, duration=duration,
-                                                  extra_info=extra_info)
+                                                  extra_info=extra_info, segment_loop=segment_loop)
         x0_dec = ldm_stable.vae_decode(w_edit)
         if "stable-audio" in ldm_stable.model_id:                       # main_run.py:187-190: the VAE output IS the audio
             return x0_dec.detach().clone().cpu().squeeze(0), x0.detach().clone().cpu(), w_edit
@@ -84,6 +85,9 @@ def main(argv=None):
     p.add_argument("--cutoff_points", type=float, nargs="*", default=None)
     p.add_argument("--fix_alpha", type=float, default=0.1)
     p.add_argument("--schedule", default="sequential", choices=["sequential", "batched"])
+    p.add_argument("--segment_loop", default="host", choices=["host", "device"],
+                   help="several target prompts with unequal --tstart: host = the step-by-step loop of the reference, "
+                        "device = one captured device loop with the fused step-and-blend kernel")
     p.add_argument("--allow_synthetic", action="store_true",
                    help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
                         "(benchmarking only: the output is noise)")
@@ -105,7 +109,7 @@ def main(argv=None):
     audio, orig, _ = edit_clip(ldm_stable, x0, args.source_prompt, args.target_prompt, args.target_neg_prompt,
                                args.cfg_src, args.cfg_tar, args.num_diffusion_steps, args.tstart, args.mode,
                                args.eta, args.schedule, cutoff_points=args.cutoff_points, fix_alpha=args.fix_alpha,
-                               duration=duration)
+                               duration=duration, segment_loop=args.segment_loop)
     torch.cuda.synchronize()
     print(f"edited {duration:.1f} s clip in {time.time() - t0:.2f} s (weights: {ldm_stable.weights_source}; "
           f"text conditioning: {ldm_stable.conditioning_source}; "

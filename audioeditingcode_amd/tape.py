@@ -526,6 +526,20 @@ class Tape:
                   [], [cur, zs, eps, ztab, cfg, coef, state, out, ctab], name=name,
                   nbytes=4 * numel * (4 * a + has_noise * a))
 
+    def step_segments(self, *, cur, zs, eps, cfg, mask, lag, alpha, traj, coef, state, numel, a, Z, P, v_pred=0, s_imm=0,
+                      c_imm=(0, 0, 0, 0, 0), s_mul=1, s_off=0, name="step_segments"):
+        """One reverse step of the `a` P-prompt segment edits in rows [0, a) of cur [K, numel], in place
+        (AED_OP_REVERSE_STEP_SEGMENTS): eps [a uncond | P blocks of a cond], cfg and mask [K, P, numel] the rows' blurred
+        guidance tensors and segment masks, zs the shared noise table [Z, numel] (None: no noise term) and traj [Z, numel]
+        the recorded trajectory, both read at row Z - step - 1 (Z = 0: one explicit row each); lag (a device int32
+        [K, P]) = Z - tstart and alpha (float [K]) = fix_alpha per row: a row with a prompt whose lag exceeds the step is
+        blended towards traj, every other row takes step()'s arithmetic with its cfg tensor."""
+        has_noise = int(zs is not None)
+        self._add(L.OP_REVERSE_STEP_SEGMENTS, [numel & 0xFFFFFFFF, numel >> 32, a, Z, s_imm, v_pred, has_noise, s_mul, s_off,
+                                               P],
+                  [0.0, *c_imm], [cur, zs, eps, lag, cfg, coef, state, mask, alpha, traj], name=name,
+                  nbytes=4 * numel * (a * (3 + 3 * P) + has_noise + 1))
+
     def drift_step_variants(self, *, cur, zs, eps, cfg, coef, state, numel, a, Z, vecs, w, n_ev, a_max, s_first, S,
                             v_pred=0, shift_np=True, mask=None, par=None, fix_mode=0, par_off=0, fix_alpha=0.0, s_imm=0,
                             c_imm=(0, 0, 0, 0, 0), s_mul=1, s_off=0, name="drift_step_variants"):

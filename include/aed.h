@@ -134,6 +134,21 @@ enum aed_opcode {
                                  slots: p0=x_t p1=zs p2=v p3=ctab p4=cfg p5=coef p6=state p7=out (null: in place) p8=hist
                                  p9=src (null: one shared table); i0,i1=numel lo/hi i2=a i3=Z i4=s_imm i5=steps i6=R i7=s_mul
                                  i8=s_off i9=N (read with src only)                                                          */
+    AED_OP_REVERSE_STEP_SEGMENTS = 35, /* one reverse step of `a` rows, each a P-prompt segment edit of ONE inverted clip at the
+                                 same loop step: rows [0, a) of x_t [K][numel] in place, eps [a uncond | P blocks of a cond]
+                                 (prompt j of row v is row a + j*a + v), per row its blurred per-element guidance tensors
+                                 cfg [K][P][numel] (eps = u + sum_p cfg_p * (c_p - u), ascending p) and ONE shared noise table;
+                                 then, for a row with a prompt that has not joined yet (lag[v][p] = Z - tstart > step), the
+                                 reference's blend towards the recorded trajectory (inversion_utils.py:308-315), in fp32 and
+                                 ascending p:  prev = sum_p mask[v][p] * (prev * (1 - af_p) + af_p * traj[Z - step - 1]),
+                                 af_p = alpha[v] where lag[v][p] > step, else 0.  A row without a lagging prompt stores the
+                                 plain step (no multiply by the mask sum) and is bit-identical to AED_OP_REVERSE_STEP with the
+                                 row's cfg tensor (EditEngine.edit_segments).  Refused: null pointers, P outside [1, 8], a
+                                 outside [1, 16], Z < 1 with a device step counter, an immediate step outside [0, Z).
+                                 slots: p0=x_t p1=zs | z | null p2=eps p3=lag int[K][P] p4=cfg p5=coef (nullable) p6=state
+                                 (nullable) p7=mask [K][P][numel] p8=alpha float[K] p9=traj [Z][numel]; i0,i1=numel lo/hi i2=a
+                                 i3=Z (rows of p1 and p9, read at Z - step - 1; 0: both are explicit rows, without p6 only)
+                                 i4=s_imm i5=v_pred i6=has_noise i7=s_mul i8=s_off i9=P; f1..f5=c0..c4 (when p5 is null)     */
     AED_OP_COUNT
 };
 

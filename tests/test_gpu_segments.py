@@ -1,0 +1,241 @@
+"""Segment edits with per-segment start steps as rows of a device loop (AED_OP_REVERSE_STEP_SEGMENTS,
+EditEngine.edit_segments, segments.inversion_reverse_segments, inversion_reverse_process(segment_loop="device")): the step
+kernel bit for bit against its plain-torch statement (tests/segment_step_ref.py) and, where no prompt lags, against opcode
+13 per row; the loop against the host-driven loop, the CPU oracle, the single loop and its own one-row calls."""
+import ctypes
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+import segment_step_ref as ref                                              # noqa: E402
+from audioeditingcode_amd import _lib as L                                  # noqa: E402
+from audioeditingcode_amd import models                                     # noqa: E402
+from audioeditingcode_amd.ddm_inversion import inversion_forward_process, inversion_reverse_process  # noqa: E402
+from audioeditingcode_amd.ddm_inversion.inversion_utils import _segment_tensors, conditioning_from_text  # noqa: E402
+from audioeditingcode_amd.editing import EditEngine                         # noqa: E402
+from audioeditingcode_amd.scheduler import DDIMScheduler, step_coefficients  # noqa: E402
+from audioeditingcode_amd.segments import inversion_reverse_segments        # noqa: E402
+from audioeditingcode_amd.tape import Tape                                  # noqa: E402
+from oracle import loops as oloops, unet as ounet                           # noqa: E402
+from oracle.scheduler import OracleDDIMScheduler                            # noqa: E402
+from conftest import oracle_run                                             # noqa: E402
+
+DEV = "cuda:0"
+
+
+def rel(a, b):
+    return ((a - b).norm() / b.norm().clamp_min(1e-12)).item()
+
+
+# ------------------------------------------------------------------------------------------------ 1. the step kernel
+NUMEL, Z, STEP = 1037, 5, 3                                                  # 1037: a grid-stride tail (4 x 256 + 13)
+
+
+def _lags(a, P, how):
+    """lag [a + 1][P] for loop step STEP.  "none": no prompt lags; "some": prompt p of row v lags iff (v + p) % 3 == 0 (rows
+    with and without a lagging prompt in one launch); "all_but_one": every prompt but p = v % P lags."""
+    lag = torch.zeros(a + 1, P, dtype=torch.int32)
+    for v in range(a):
+        for p in range(P):
+            on = {"none": False, "some": (v + p) % 3 == 0, "all_but_one": p != v % P}[how]
+            lag[v, p] = STEP + 1 + (v + p) % 2 if on else STEP - (v + p) % 3
+    return lag
+
+
+@pytest.mark.parametrize("a, P", [(1, 2), (3, 3), (5, 2)])
+@pytest.mark.parametrize("v_pred", [0, 1])
+def test_segments_step_is_bitwise_its_torch_statement_and_opcode_13_where_nothing_lags(a, P, v_pred):
+    """With and without noise; an immediate step with immediate coefficients and a device counter (step = 1 * 2 + 1) with a
+    coefficient table; no / some / all-but-one lagging prompts; alpha 0 and 0.2 by row.  Row a of the buffers is not part of
+    the launch and stays as it is."""
+    g = torch.Generator().manual_seed(100 * a + 10 * P + v_pred)
+    sched = DDIMScheduler()
+    sched.set_timesteps(20)
+    coef = torch.stack([step_coefficients(sched, int(t), 1.0) for t in sched.timesteps[-Z:]]).float().contiguous()
+    K = a + 1
+    cur0 = torch.randn(K, NUMEL, generator=g)
+    eps = torch.randn(a * (1 + P), NUMEL, generator=g)
+    cfg = torch.rand(K, P, NUMEL, generator=g) * 12
+    mask = torch.rand(K, P, NUMEL, generator=g)
+    zs = torch.randn(Z, NUMEL, generator=g)
+    traj = torch.randn(Z, NUMEL, generator=g)
+    alpha = torch.tensor([0.2 if v % 2 == 0 else 0.0 for v in range(K)], dtype=torch.float32)
+    if a > 1:
+        alpha[a - 1] = 0.2
+    state = torch.tensor([1, 0, 0, 0], dtype=torch.int32)
+    dev = lambda t: None if t is None else t.to(DEV)                                              # noqa: E731
+    for how in ("none", "some", "all_but_one"):
+        lag = _lags(a, P, how)
+        for noise in (True, False):
+            for counter in (False, True):
+                step_kw = dict(coef=coef, state=state, s_mul=2, s_off=1) if counter else \
+                    dict(coef=None, state=None, s_imm=STEP, c_imm=tuple(float(c) for c in coef[STEP][:5]))
+                want = cur0.clone()                                          # the torch statement on CPU buffers
+                tc = Tape("cpu")
+                tc.step_segments(cur=want, zs=zs if noise else None, eps=eps, cfg=cfg, mask=mask, lag=lag, alpha=alpha,
+                                 traj=traj, numel=NUMEL, a=a, Z=Z, P=P, v_pred=v_pred, **step_kw)
+                ref.segments_step_cpu(tc.ops[0])
+                bufs = dict(eps=dev(eps), cfg=dev(cfg), mask=dev(mask), lag=dev(lag), alpha=dev(alpha), traj=dev(traj))
+                dkw = {k: dev(v) if torch.is_tensor(v) else v for k, v in step_kw.items()}
+                got = cur0.to(DEV)
+                tp = Tape(DEV)
+                tp.step_segments(cur=got, zs=dev(zs) if noise else None, numel=NUMEL, a=a, Z=Z, P=P, v_pred=v_pred, **bufs,
+                                 **dkw)
+                tp.run()
+                torch.cuda.synchronize()
+                what = (how, noise, counter)
+                assert torch.isfinite(want).all(), what
+                assert torch.equal(got.cpu(), want), (what, (got.cpu() - want).abs().max().item())
+                assert torch.equal(got[a:].cpu(), cur0[a:]) and not torch.equal(got[:a].cpu(), cur0[:a]), what
+                if how != "none":
+                    continue
+                # no lagging prompt: opcode 13 per row on the same inputs with the row's cfg tensor
+                one = torch.full((a, NUMEL), float("nan"), device=DEV)
+                tq = Tape(DEV)
+                for v in range(a):
+                    eps_c = torch.stack([bufs["eps"][a + j * a + v] for j in range(P)]).contiguous()
+                    tq.step(L.OP_REVERSE_STEP, xts=cur0[v].to(DEV), zs=dev(zs) if noise else None, eps_u=bufs["eps"][v],
+                            eps_c=eps_c, cfg=bufs["cfg"][v].contiguous(), out=one[v], numel=NUMEL, P=P,
+                            T=Z if noise else 0, v_pred=v_pred, flag=int(noise), **dkw)
+                tq.run()
+                torch.cuda.synchronize()
+                assert torch.equal(got[:a], one), (what, (got[:a] - one).abs().max().item())
+
+
+def test_segments_step_launcher_refusals_on_the_device():
+    """Refused before anything is launched, with live device pointers: the stream stays usable."""
+    t = torch.zeros(4, 64, device=DEV)
+    lag = torch.zeros(4, 2, dtype=torch.int32, device=DEV)
+    state = torch.zeros(4, dtype=torch.int32, device=DEV)
+    lib, st = L.lib(), L.current_stream_ptr()
+    base = dict(cur=t, zs=t, eps=t, cfg=t, mask=t, lag=lag, alpha=t, traj=t, coef=t, state=state, numel=8, a=2, Z=4, P=2)
+    for kw, what in ((dict(P=9), "P 9 outside [1, 8]"), (dict(a=17), "a 17 outside [1, 16]"), (dict(mask=None), "null pointer"),
+                     (dict(Z=0), "Z 0, the device counter"), (dict(state=None, s_imm=4), "step 4 outside [0, Z = 4)")):
+        tp = Tape(DEV)
+        tp.step_segments(**{**base, **kw})
+        assert lib.aed_launch(ctypes.byref(tp.ops[0]), st) != 0
+        assert what in lib.aed_last_error().decode(), what
+    torch.cuda.synchronize()
+    assert float(t.sum()) == 0.0
+
+
+# ------------------------------------------------------------------------------------------------ 2. the loop
+T = 8
+
+
+@pytest.fixture(scope="module")
+def clip():
+    """test_two_prompt_segments_equal_and_unequal_tstart_on_the_gpu's inversion (tests/test_gpu_e2e.py): the same seeds,
+    prompts, cfgs and cutoff."""
+    m = models.load_model("tiny/audioldm2", DEV, T, seed=0)
+    w0 = torch.randn(1, 8, 32, 16, generator=torch.Generator().manual_seed(4)) * 0.7
+    torch.manual_seed(8)
+    with torch.inference_mode():
+        _, zs, wts, _ = inversion_forward_process(m, w0.to(DEV), etas=1.0, prompts=["rain", "wind"], cfg_scales=[3.0, 2.0],
+                                                  num_inference_steps=T, numerical_fix=True, cutoff_points=[0.4])
+    return dict(m=m, w0=w0, zs=zs.clone(), wts=wts.clone())
+
+
+def _oracle_wrapper(m):
+    cfg, sd = m.family["unet"], m.state_dicts["unet"]
+    osched = OracleDDIMScheduler()
+    osched.set_timesteps(T)
+
+    def unet_fn(x, t, cond):
+        hs, cl, mk = cond
+        ex = lambda v: None if v is None else v.cpu().expand(x.shape[0], *v.shape[1:])      # noqa: E731
+        return ounet.unet_forward(cfg, sd, x, t, encoder_hidden_states=ex(hs), encoder_hidden_states_1=ex(cl),
+                                  encoder_attention_mask_1=ex(mk))[0]
+    return oloops.OracleWrapper(osched, unet_fn)
+
+
+def _reverse(c, tstart, **kw):
+    args = dict(xT=c["wts"], tstart=torch.tensor(tstart), fix_alpha=0.2, etas=1.0, prompts=["jazz", "rock"],
+                neg_prompts=[""], cfg_scales=[9.0, 6.0], zs=c["zs"][:max(tstart)], cutoff_points=[0.5])
+    args.update(kw)
+    with torch.inference_mode():
+        w, _ = inversion_reverse_process(c["m"], **args)
+    torch.cuda.synchronize()
+    return w
+
+
+def test_device_loop_matches_the_host_driven_loop_and_the_oracle(clip):
+    """tstarts [5, 3]: segment_loop="device" against the default host-driven call (2e-3, test_gpu_variants.py's bar for a
+    batched loop against the single loop) and against the oracle's loop (5e-3, test_gpu_e2e.py's bar; the committed run
+    e2e_two_prompt_segments_T8, same closure and probe)."""
+    m, w0 = clip["m"], clip["w0"]
+    ed = m.editor(32, 16)
+    ed.clear_plans()
+    w_host = _reverse(clip, [5, 3])
+    assert not ed._plans                                                     # the default stays host-driven: no loop plan
+    w_dev = _reverse(clip, [5, 3], segment_loop="device")
+    assert [k[0] for k in ed._plans] == ["segments"]
+    print("device vs host", rel(w_dev, w_host))
+    assert w_dev.shape == (1, 8, 32, 16) and rel(w_dev, w_host) < 2e-3, rel(w_dev, w_host)
+    assert rel(w_dev, _reverse(clip, [5, 3], fix_alpha=0.0)) > 1e-3              # the blend did act
+    ow = _oracle_wrapper(m)
+    enc = lambda p, **k: tuple(None if t is None else t.cpu() for t in m.encode_text(p, **k))     # noqa: E731
+    xts0 = ow.sample_xts_from_x0(w0, T, generator=torch.Generator().manual_seed(8))
+    tgt = enc(["jazz", "rock"])
+    tstarts = ([5, 5], [5, 3])
+
+    def oracle():
+        _, zs_o, xts_o = oloops.invert(ow, w0, enc(["rain", "wind"]), enc([""]), [3.0, 2.0], T, xts=xts0, n_prompts=2,
+                                       cutoff_points=[0.4], prompt_empty=[False, False])
+        return zs_o, [oloops.edit(ow, xts_o, torch.tensor(ts), tgt, enc([""]), [9.0, 6.0], zs_o[:max(ts)], eta=1.0, n_prompts=2,
+                                  cutoff_points=[0.5], fix_alpha=0.2) for ts in tstarts]
+    _, w_os = oracle_run("e2e_two_prompt_segments_T8", oracle, xts0)
+    print("device vs oracle", rel(w_dev.cpu(), w_os[1]))
+    assert rel(w_dev.cpu(), w_os[1]) < 5e-3, rel(w_dev.cpu(), w_os[1])
+
+
+def _row(m, tstarts, cfgs, cuts, fa, prompts=("jazz", "rock")):
+    cfg_t, masks = _segment_tensors(len(prompts), (8, 32, 16), cfgs, cuts, torch.float32)
+    return (list(tstarts), conditioning_from_text(m, m.encode_text(list(prompts))),
+            conditioning_from_text(m, m.encode_text([""], negative=True)), cfg_t, masks, fa)
+
+
+def test_equal_tstarts_are_bitwise_the_single_loop_with_the_cfg_tensor(clip, monkeypatch):
+    """Without CFG row sharing EditEngine.edit runs the same U-Net engine at batch 3, and the op takes its no-blend
+    branch at every step."""
+    monkeypatch.setattr(EditEngine, "SHARE_IN_EDIT_LOOP", False)
+    m = clip["m"]
+    ed = m.editor(32, 16)
+    ed.clear_plans()
+    with torch.inference_mode():
+        xts_c, zs_c = ed.to_nhwc(clip["wts"].unsqueeze(1)), ed.to_nhwc(clip["zs"][:5].unsqueeze(1))
+        row = _row(m, [5, 5], [9.0, 6.0], [0.5], 0.2)
+        w_seg = ed.edit_segments(xts_c, zs_c, [row])
+        w_one = ed.edit(xts_c, zs_c, 5, row[1], row[2], [9.0, 6.0], eta=1.0, cfg_tensor=row[3])
+    torch.cuda.synchronize()
+    ed.clear_plans()
+    assert w_seg.shape == w_one.shape == (1, 32, 16, 8) and torch.isfinite(w_one).all()
+    assert torch.equal(w_seg, w_one), (w_seg - w_one).abs().max().item()
+
+
+def test_a_sweep_of_six_rows_matches_each_rows_own_call_and_repeats_bitwise(clip):
+    m = clip["m"]
+    edits = [dict(prompts=["jazz", "rock"], neg_prompts=[""], tstart=list(ts), cfg_scales=list(cf), cutoff_points=[0.5],
+                  fix_alpha=0.2) for ts in ((5, 3), (5, 5), (4, 2)) for cf in ((9.0, 6.0), (4.0, 12.0))]
+    with torch.inference_mode():
+        w = inversion_reverse_segments(m, clip["wts"], clip["zs"][:5], edits)
+        again = inversion_reverse_segments(m, clip["wts"], clip["zs"][:5], edits)
+        torch.cuda.synchronize()
+        assert w.shape == (6, 8, 32, 16) and torch.isfinite(w).all()
+        assert torch.equal(w, again)                                         # the loop is deterministic
+        for k, e in enumerate(edits):
+            w1 = inversion_reverse_segments(m, clip["wts"], clip["zs"][:5], [e])
+            print("row", k, rel(w[k:k + 1], w1))
+            assert rel(w[k:k + 1], w1) < 2e-3, (k, rel(w[k:k + 1], w1))
+    assert all(not torch.equal(w[i], w[j]) for i in range(6) for j in range(i))
+    assert rel(w[0:1], _reverse(clip, [5, 3])) < 2e-3                         # and row 0 is the host-driven edit
+
+
+def test_three_prompts_match_the_host_driven_loop(clip):
+    kw = dict(prompts=["jazz", "rock", "rain"], cfg_scales=[9.0, 6.0, 3.0], cutoff_points=[0.3, 0.7])
+    w_dev = _reverse(clip, [6, 6, 2], segment_loop="device", **kw)
+    w_host = _reverse(clip, [6, 6, 2], **kw)
+    print("P = 3: device vs host", rel(w_dev, w_host))
+    assert rel(w_dev, w_host) < 2e-3, rel(w_dev, w_host)

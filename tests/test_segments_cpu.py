@@ -1,0 +1,406 @@
+"""Host side of the segment-edit loop (the opcode-35 record, editing.segments_plan, EditEngine.edit_segments, segments.py,
+inversion_reverse_process' segment_loop switch, the main_run_segments CLI): no GPU needed.  The loops run on the oracle's
+tape interpreter; the segments step is stated in tests/segment_step_ref.py."""
+import ctypes
+import json
+import os
+import re
+from types import SimpleNamespace
+
+import pytest
+import torch
+
+import segment_step_ref as ref
+from audioeditingcode_amd import _lib as L
+from audioeditingcode_amd import configs, main_run, main_run_segments, models, segments, weights
+from audioeditingcode_amd.ddm_inversion import inversion_forward_process, inversion_reverse_process
+from audioeditingcode_amd.ddm_inversion.inversion_utils import _segment_tensors
+from audioeditingcode_amd.editing import Conditioning, EditEngine, segments_plan
+from audioeditingcode_amd.scheduler import DDIMScheduler
+from audioeditingcode_amd.tape import Tape
+from oracle import loops as oloops
+from oracle import tape_interp
+from oracle import unet as ounet
+from oracle.scheduler import OracleDDIMScheduler
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+T, LH, LW, LC = 6, 8, 8, 8
+
+
+def _rel(a, b):
+    return ((a - b).norm() / b.norm().clamp_min(1e-12)).item()
+
+
+# ------------------------------------------------------------------------------------------------ the op record
+def test_op_record_header_and_launcher_refusals():
+    if not os.path.exists(L.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    hdr = open(os.path.join(ROOT, "include", "aed.h")).read()
+    assert re.search(r"AED_OP_REVERSE_STEP_SEGMENTS\s*=\s*35\b", hdr)
+    assert L.OP_REVERSE_STEP_SEGMENTS == 35 and len(L.OP_NAMES) == 31
+    tp = Tape("cpu")                                                     # the op's slots, as include/aed.h lists them
+    f = [torch.zeros(64) for _ in range(8)]
+    lag = torch.zeros(6, dtype=torch.int32)
+    state = torch.zeros(4, dtype=torch.int32)
+    tp.step_segments(cur=f[0], zs=f[1], eps=f[2], cfg=f[3], mask=f[4], lag=lag, alpha=f[5], traj=f[6], coef=f[7],
+                     state=state, numel=3, a=2, Z=5, P=3, v_pred=1, s_mul=2, s_off=1)
+    tp.step_segments(cur=f[0], zs=None, eps=f[2], cfg=f[3], mask=f[4], lag=lag, alpha=f[5], traj=f[6], coef=None,
+                     state=None, numel=3, a=2, Z=5, P=3, s_imm=4, c_imm=(1, 2, 3, 4, 5))
+    op = tp.ops[0]
+    assert op.code == 35 and tp.meta[0]["name"] == "step_segments"
+    assert list(op.i[:10]) == [3, 0, 2, 5, 0, 1, 1, 2, 1, 3]
+    assert [op.p[k] for k in range(10)] == [t.data_ptr() for t in (f[0], f[1], f[2], lag, f[3], f[7], state, f[4], f[5], f[6])]
+    op = tp.ops[1]
+    assert list(op.i[:10]) == [3, 0, 2, 5, 4, 0, 0, 1, 0, 3] and [op.f[k] for k in range(6)] == [0, 1, 2, 3, 4, 5]
+    assert op.p[1] is None and op.p[5] is None and op.p[6] is None
+    # the built library refuses bad records before it launches anything (no device is touched)
+    lib = L.lib()
+    assert lib.aed_version() == 4
+
+    def launch(**kw):
+        rec = L.aed_op()
+        rec.code = 35
+        for k, v in enumerate([8, 0, kw.get("a", 2), kw.get("Z", 4), kw.get("s", 0), 0, 0, 1, 0, kw.get("P", 2)]):
+            rec.i[k] = v
+        for k in (0, 2, 3, 4, 7, 8, 9):
+            rec.p[k] = 64
+        for k in kw.get("null", ()):
+            rec.p[k] = None
+        if kw.get("state"):
+            rec.p[6] = 64
+        rc = lib.aed_launch(ctypes.byref(rec), None)
+        return rc, lib.aed_last_error().decode()
+    rc, msg = launch(P=9)
+    assert rc != 0 and "P 9 outside [1, 8]" in msg
+    rc, msg = launch(P=0)
+    assert rc != 0 and "P 0 outside [1, 8]" in msg
+    rc, msg = launch(a=17)
+    assert rc != 0 and "a 17 outside [1, 16]" in msg
+    rc, msg = launch(null=(7,))
+    assert rc != 0 and "reverse_step_segments: null pointer" in msg and "mask" in msg
+    rc, msg = launch(null=(9,))
+    assert rc != 0 and "reverse_step_segments: null pointer" in msg
+    rc, msg = launch(Z=0, state=True)
+    assert rc != 0 and "Z 0, the device counter indexes tables of Z >= 1 rows" in msg
+    rc, msg = launch(Z=4, s=4)
+    assert rc != 0 and "step 4 outside [0, Z = 4)" in msg
+
+
+# ------------------------------------------------------------------------------------------------ the blend arithmetic
+@pytest.mark.parametrize("P", [2, 3])
+def test_blend_statement_equals_the_reference_lines(P):
+    """tests/segment_step_ref.blend (what the kernel is compared with bit for bit) against inversion_utils.py:308-315
+    transcribed literally, at every step of a row's loop (torch's sum(axis=0) over 2 or 3 slices is the left-to-right sum)."""
+    g = torch.Generator().manual_seed(P)
+    C, H, W, Tn = 3, 5, 7, 7
+    xT = torch.randn(Tn + 1, C, H, W, generator=g)
+    masks = torch.rand(P, C, H, W, generator=g)
+    for tstart, fa in (([6, 3, 5][:P], 0.2), ([4, 6, 6][:P], 0.1), ([5, 5, 5][:P], 0.3), ([6, 2, 2][:P], 0.0)):
+        ts = torch.tensor(tstart)
+        Z = int(ts.max())
+        alpha = torch.tensor(fa, dtype=torch.float32)
+        for it in range(Z):
+            xt = torch.randn(1, C, H, W, generator=g)
+            want = ref.reference_blend(xt, xT, masks, ts, fa, it)
+            got = ref.blend(xt.reshape(-1), masks.reshape(P, -1), [Z - t for t in tstart], alpha, it,
+                            xT[Z - it - 1].reshape(-1))
+            assert got.dtype == torch.float32 and torch.equal(got.reshape(want.shape), want), (tstart, it)
+            if it >= Z - min(tstart):                                    # no prompt lags: the very same values
+                assert got is xt.reshape(-1) or torch.equal(got, xt.reshape(-1))
+                assert not torch.equal(want, (masks * xt).sum(0, keepdim=True))
+    # 1 - af is an fp32 subtraction from the fp32 alpha (the reference's `1 - apply_fix` on a float32 tensor)
+    a32 = torch.tensor(0.1, dtype=torch.float32)
+    assert (1 - a32).dtype == torch.float32 and (torch.tensor([True]) * 0.1).dtype == torch.float32
+    prev, tr = torch.full((4,), 3.0), torch.full((4,), -1.0)
+    got = ref.blend(prev, torch.ones(1, 4), [1], a32, 0, tr)
+    assert torch.equal(got, prev * (1 - a32) + a32 * tr)
+    # the guidance combine: the reference's `(cfg * (cond - uncond)).sum(axis=0)` (inversion_utils.py:276-281)
+    u, c, cf = torch.randn(1, 40, generator=g), torch.randn(P, 40, generator=g), torch.rand(P, 40, generator=g) * 9
+    assert torch.equal(ref.combine(u[0], c, cf), (u + (cf * (c - u.expand(P, -1))).sum(axis=0).unsqueeze(0))[0])
+
+
+def test_sum_over_up_to_four_slices_is_left_to_right():
+    """What makes the kernel's ascending-p sums (cfg_combine's order) the reference's `.sum(axis=0)` bit for bit.  It holds
+    for P <= 4 on torch's CPU reduction; from P = 5 on that reduction keeps several partial sums, so there the kernel and
+    the host-driven loop agree to rounding only (opcode 13's cfg_combine has the same property)."""
+    g = torch.Generator().manual_seed(0)
+    for P in range(1, 5):
+        x = torch.randn(P, 2, 9, 5, generator=g) * torch.logspace(-3, 3, P).reshape(P, 1, 1, 1)
+        acc = x[0]
+        for j in range(1, P):
+            acc = acc + x[j]
+        assert torch.equal(x.sum(axis=0), acc), P
+
+
+# ------------------------------------------------------------------------------------------------ plan and refusals
+def _cond(rows=1, L1=3):
+    return Conditioning(ehs0=torch.zeros(rows, 8, 4), ehs1=torch.zeros(rows, L1, 6), mask1=torch.ones(rows, L1))
+
+
+def _row(tstarts, fa=0.1, shape=(LC, LH, LW)):
+    P = len(tstarts)
+    cfg_t, masks = _segment_tensors(P, shape, [3.0] * P, None, torch.float32)
+    return (list(tstarts), _cond(P), _cond(1), cfg_t, masks, fa)
+
+
+def test_segments_plan_orders_rows_by_their_largest_tstart():
+    p = segments_plan([_row([4, 3]), _row([2, 4]), _row([3, 3]), _row([1, 2]), _row([4, 4])], 5, "audioldm2", (LH, LW, LC))
+    assert p["P"] == 2 and p["tstarts"] == [[4, 3], [2, 4], [3, 3], [1, 2], [4, 4]]
+    assert p["order"] == [0, 1, 4, 2, 3]
+    assert [(s["tstart"], s["a"], s["join"], s["start"], s["steps"]) for s in p["segs"]] == [
+        (4, 3, (0, 3), 0, 1), (3, 4, (3, 4), 1, 1), (2, 5, (4, 5), 2, 2)]
+
+
+@pytest.mark.parametrize("rows, kw, what", [
+    ([], {}, "list of rows is empty"),
+    ([_row([4, 3]), _row([4, 3, 2])], {}, r"rows with \[2, 3\] prompts in one call"),
+    ([_row([3] * 9)], {}, "9 prompts per row, the segments step takes 1 to 8"),
+    ([_row([4, 3])] * 11, {}, "11 rows of 2 prompts are 33 U-Net rows, at most 32"),
+    ([_row([2, 2, 2])] * 9, {}, "9 rows of 3 prompts are 36 U-Net rows, at most 32"),
+    ([_row([4, 0])], {}, r"row 0 has tstart 0 outside \[1, 5\]"),
+    ([_row([4, 3]), _row([6, 3])], {}, r"row 1 has tstart 6 outside \[1, 5\] \(the number of noise maps zs holds\)"),
+    ([_row([4, 3])], dict(kind="stable_audio"), "edit_segments: engine kind 'stable_audio' is not supported"),
+    ([_row([4, 3], shape=(LC, LH + 1, LW))], {}, "row 0 has a cfg tensor"),
+    ([([4, 3], _cond(1), _cond(1), *_row([4, 3])[3:])], {}, "row 0 has 1 target and 1 negative conditioning rows, expected 2 and 1"),
+])
+def test_segments_plan_refusals(rows, kw, what):
+    with pytest.raises(ValueError, match=what):
+        segments_plan(rows, 5, kw.get("kind", "audioldm2"), (LH, LW, LC))
+
+
+def test_engine_refusals():
+    eng = EditEngine.__new__(EditEngine)
+    eng.kind, eng.sched = "audioldm2", DDIMScheduler()
+    eng.sched.set_timesteps(T)
+    eng.C, eng.H, eng.W = LC, LH, LW
+    xts, zs = torch.zeros(T + 1, 1, LH, LW, LC), torch.zeros(5, 1, LH, LW, LC)
+    with pytest.raises(ValueError, match="edit_segments edits ONE inverted clip"):
+        eng.edit_segments(torch.zeros(T + 1, 2, LH, LW, LC), zs, [_row([4, 3])])
+    with pytest.raises(ValueError, match=r"tstart 6 outside \[1, 5\]"):
+        eng.edit_segments(xts, zs, [_row([6, 3])])
+    with pytest.raises(ValueError, match="33 U-Net rows"):
+        eng.edit_segments(xts, zs, [_row([4, 3])] * 11)
+    with pytest.raises(ValueError, match="zero at some steps"):
+        eng.edit_segments(xts, zs, [_row([4, 3])], eta=[1.0, 0.0, 1.0, 1.0])
+    eng.kind = "stable_audio"
+    with pytest.raises(ValueError, match="engine kind 'stable_audio'"):
+        eng.edit_segments(xts, zs, [_row([4, 3])])
+    with pytest.raises(NotImplementedError, match="inversion_reverse_segments: Stable Audio is not supported"):
+        segments.inversion_reverse_segments(SimpleNamespace(kind="stable_audio"), xts[:, 0], zs[:, 0], [{}])
+    m = SimpleNamespace(kind="tango")
+    ok = dict(prompts=["a", "b"], neg_prompts=[""], tstart=[4, 3], cfg_scales=[3.0], cutoff_points=None, fix_alpha=0.1)
+    x4, z4 = torch.zeros(T + 1, LC, LH, LW), torch.zeros(5, LC, LH, LW)
+    for bad, what in ((dict(ok, tstart=[4, 3, 2]), "3 tstart values for 2 prompts"),
+                      (dict(ok, cfg_scales=[1.0, 2.0, 3.0]), "3 cfg_scales values for 2 prompts"),
+                      (dict(ok, cutoff_points=[0.5, 0.7]), "cutoff points"), (dict(ok, cutoff_points=[1.0]), "cutoff points"),
+                      (dict(ok, tstart=[4, 6]), r"tstart 6 outside \[1, 5\]"), (dict(ok, neg_prompts=["", ""]), "2 negative prompts"),
+                      ({k: v for k, v in ok.items() if k != "fix_alpha"}, "has the keys")):
+        with pytest.raises(ValueError, match=what):
+            segments.inversion_reverse_segments(m, x4, z4, [bad])
+    with pytest.raises(ValueError, match="list of edits is empty"):
+        segments.inversion_reverse_segments(m, x4, z4, [])
+
+
+# ------------------------------------------------------------------------------------------------ the loops on CPU
+@pytest.fixture
+def cpu_loops(cpu_stack, monkeypatch):
+    monkeypatch.setitem(tape_interp.DISPATCH, 35, ref.segments_step_cpu)
+
+
+class _CpuAudioLDM2(models.AudioLDM2Wrapper):
+    def _require_device(self):           # test instrumentation only: the product class refuses a CPU device
+        pass
+
+
+def _model():
+    m = _CpuAudioLDM2(model_id="tiny/audioldm2", device="cpu", seed=0)
+    m.load_scheduler()
+    m.model.scheduler.set_timesteps(T, device=None)
+    return m
+
+
+def _oracle_wrapper(m):
+    cfg, sd = m.family["unet"], m.state_dicts["unet"]
+    osched = OracleDDIMScheduler()
+    osched.set_timesteps(T)
+
+    def unet_fn(x, t, cond):
+        hs, cl, mk = (v.expand(x.shape[0], *v.shape[1:]) for v in cond)
+        return ounet.unet_forward(cfg, sd, x, t, encoder_hidden_states=hs, encoder_hidden_states_1=cl,
+                                  encoder_attention_mask_1=mk)[0]
+    return oloops.OracleWrapper(osched, unet_fn)
+
+
+def test_one_row_matches_the_host_driven_loop_and_the_oracle(cpu_loops):
+    """tstarts [4, 3] through inversion_reverse_process: segment_loop="device" against the default host-driven
+    _reverse_with_hooks on the same wrapper (the same torch math at another U-Net batch size: 1e-4, the bar of
+    test_grid_cpu.py) and against the oracle's loop (2e-3, the bar of test_wrapper_cpu.py)."""
+    m = _model()
+    ow = _oracle_wrapper(m)
+    w0 = torch.randn(1, LC, LH, LW, generator=torch.Generator().manual_seed(4)) * 0.7
+    torch.manual_seed(8)
+    _, zs, wts, _ = inversion_forward_process(m, w0, etas=1.0, prompts=["rain"], cfg_scales=[3.0],
+                                              num_inference_steps=T, numerical_fix=True)
+    kw = dict(xT=wts, tstart=torch.tensor([4, 3]), fix_alpha=0.2, etas=1.0, prompts=["jazz", "rock and roll"],
+              neg_prompts=[""], cfg_scales=[9.0, 6.0], zs=zs[:4], cutoff_points=[0.5])
+    w_host, _ = inversion_reverse_process(m, **kw)
+    w_dev, zs_out = inversion_reverse_process(m, **kw, segment_loop="device")
+    assert zs_out is kw["zs"] and w_dev.shape == w_host.shape == (1, LC, LH, LW)
+    assert _rel(w_dev, w_host) < 1e-4, _rel(w_dev, w_host)
+    xts0 = ow.sample_xts_from_x0(w0, T, generator=torch.Generator().manual_seed(8))
+    _, zs_o, xts_o = oloops.invert(ow, w0, m.encode_text(["rain"]), m.encode_text([""]), [3.0], T, xts=xts0)
+    w_o = oloops.edit(ow, xts_o, torch.tensor([4, 3]), m.encode_text(["jazz", "rock and roll"]), m.encode_text([""]),
+                      [9.0, 6.0], zs_o[:4], eta=1.0, n_prompts=2, cutoff_points=[0.5], fix_alpha=0.2)
+    assert _rel(w_dev, w_o) < 2e-3, _rel(w_dev, w_o)
+    assert _rel(w_dev, inversion_reverse_process(m, **dict(kw, fix_alpha=0.0))[0]) > 1e-3      # the blend did act
+    # equal tstart is routed as before, whatever the switch says; hooks and the general case name their reason
+    same = dict(kw, tstart=torch.tensor([4, 4]))
+    assert torch.equal(inversion_reverse_process(m, **same, segment_loop="device")[0], inversion_reverse_process(m, **same)[0])
+    with pytest.raises(ValueError, match="does not run h-space / skip-connection hooks"):
+        inversion_reverse_process(m, **kw, segment_loop="device", zero_out_resconns=[1])
+    with pytest.raises(ValueError, match="a start index that differs from the number of noise maps"):
+        inversion_reverse_process(m, **dict(kw, zs=zs[:5]), segment_loop="device")
+    with pytest.raises(ValueError, match="segment_loop 'gpu'"):
+        inversion_reverse_process(m, **kw, segment_loop="gpu")
+    # the library function on two edits of different P: each equals its own call
+    e2 = dict(prompts=["jazz", "rock and roll"], neg_prompts=[""], tstart=[4, 3], cfg_scales=[9.0, 6.0], cutoff_points=[0.5],
+              fix_alpha=0.2)
+    e3 = dict(prompts=["jazz", "pop", "rain"], neg_prompts=["noise"], tstart=[2, 4, 3], cfg_scales=[5.0], cutoff_points=None,
+              fix_alpha=0.1)
+    seen = []
+    enc = m.encode_text
+    m.encode_text = lambda p, **k: (seen.append((tuple(p), k.get("negative", False))) or enc(p, **k))
+    both = segments.inversion_reverse_segments(m, wts, zs[:4], [e3, e2, e2])
+    assert sorted(seen) == sorted({(("jazz",), False), (("pop",), False), (("rain",), False), (("rock and roll",), False),
+                                   (("",), True), (("noise",), True)})       # every distinct prompt once
+    assert both.shape == (3, LC, LH, LW) and torch.equal(both[1], both[2])
+    assert _rel(both[1:2], w_dev) < 1e-4
+    w3, _ = inversion_reverse_process(m, xT=wts, tstart=torch.tensor([2, 4, 3]), fix_alpha=0.1, etas=1.0,
+                                      prompts=e3["prompts"], neg_prompts=["noise"], cfg_scales=[5.0], zs=zs[:4])
+    assert _rel(both[0:1], w3) < 1e-4, _rel(both[0:1], w3)
+
+
+def _engine():
+    cfg = configs.tiny_family("audioldm2")["unet"]
+    sd = weights.random_state_dict(weights.unet_param_shapes(cfg), seed=0)
+    sched = DDIMScheduler()
+    sched.set_timesteps(T)
+    return EditEngine(cfg, sd, sched, "cpu", LH, LW, "audioldm2")
+
+
+def _inputs(seed=5):
+    g = torch.Generator().manual_seed(seed)
+    mk = lambda rows, L1: Conditioning(ehs0=torch.randn(rows, 8, 48, generator=g),                # noqa: E731
+                                       ehs1=torch.randn(rows, L1, 64, generator=g), mask1=torch.ones(rows, L1))
+    xts = torch.randn(T + 1, 1, LH, LW, LC, generator=g)
+    zs = torch.randn(4, 1, LH, LW, LC, generator=g)
+    return g, mk, xts, zs
+
+
+def test_rows_of_one_loop_match_their_own_calls_and_the_plan_is_reused(cpu_loops):
+    """Five rows with maxima 4 / 4 / 3 / 2 / 4 (three loop segments; one row with equal tstarts, fix_alpha 0 among the
+    rows) and a P = 3 call: every row against its own one-row call (fp32 torch math on both sides, another U-Net batch
+    size: 1e-4).  Other tstarts of the same maxima reuse the plan and equal a fresh engine's result."""
+    g, mk, xts, zs = _inputs()
+    eng = _engine()
+    unc = mk(1, 1)
+    tgts = [mk(2, 5), mk(2, 7), mk(2, 3)]
+
+    def row(k, tstarts, cfgs, cuts, fa):
+        cfg_t, masks = _segment_tensors(2, (LC, LH, LW), cfgs, cuts, torch.float32)
+        return (tstarts, tgts[k % 3], unc, cfg_t, masks, fa)
+    spec = [([4, 3], [9.0, 6.0], [0.5], 0.2), ([2, 4], [3.0, 12.0], [0.4], 0.0), ([3, 1], [5.0, 5.0], None, 0.1),
+            ([2, 1], [7.0, 2.0], [0.6], 0.3), ([4, 4], [6.0, 9.0], [0.5], 0.2)]
+    rows = [row(k, *s) for k, s in enumerate(spec)]
+    w = eng.edit_segments(xts, zs, rows)
+    assert w.shape == (5, LH, LW, LC) and torch.isfinite(w).all()
+    segs = [p for key, p in eng._plans.items() if key[0] == "segments"][0]["segs"]
+    assert len(segs) == 3 and [sp["eng"].B for sp in segs] == [9, 12, 15]
+    for k in range(5):
+        w1 = eng.edit_segments(xts, zs, [rows[k]])
+        assert _rel(w[k:k + 1], w1) < 1e-4, (k, _rel(w[k:k + 1], w1))
+    assert all(not torch.equal(w[i], w[j]) for i in range(5) for j in range(i))
+    # the row with equal tstarts never blends: it is the single loop with the cfg tensor
+    w_eq = eng.edit(xts, zs, 4, tgts[1], unc, None, cfg_tensor=rows[4][3])
+    assert _rel(w[4:5], w_eq) < 1e-4, _rel(w[4:5], w_eq)
+    # fix_alpha 0 leaves the masks' sum, which the blur keeps at 1 up to rounding: the row is its equal-tstart edit
+    assert _rel(w[1:2], eng.edit_segments(xts, zs, [row(1, [4, 4], *spec[1][1:])])) < 1e-4
+    assert _rel(w[0:1], eng.edit_segments(xts, zs, [row(0, [4, 4], *spec[0][1:])])) > 1e-3       # fix_alpha 0.2 is not
+    # other tstarts of the same maxima: same plan (lag is data), equal to a fresh engine
+    spec2 = [([4, 1], *spec[0][1:]), ([4, 2], *spec[1][1:]), ([1, 3], *spec[2][1:]), ([1, 2], *spec[3][1:]),
+             ([3, 4], *spec[4][1:])]
+    rows2 = [row(k, *s) for k, s in enumerate(spec2)]
+    n_plans = len(eng._plans)
+    w2 = eng.edit_segments(xts, zs, rows2)
+    assert len(eng._plans) == n_plans and not torch.equal(w2, w)
+    assert torch.equal(w2, _engine().edit_segments(xts, zs, rows2))
+    assert torch.equal(eng.edit_segments(xts, zs, rows), w)
+    # n_steps stops early; eta 0 reads no noise
+    part = eng.edit_segments(xts, zs, rows[:1], n_steps=1)
+    assert not torch.equal(part, w[:1]) and torch.isfinite(part).all()
+    w_0 = eng.edit_segments(xts, None, rows[:1], eta=0.0)
+    assert torch.isfinite(w_0).all() and not torch.equal(w_0, w[:1])
+    # P = 3
+    t3 = [mk(3, 4), mk(3, 6)]
+    rows3 = []
+    for k, (ts, fa) in enumerate((([3, 4, 2], 0.2), ([2, 2, 3], 0.1))):
+        cfg_t, masks = _segment_tensors(3, (LC, LH, LW), [9.0, 6.0, 3.0], [0.3, 0.7], torch.float32)
+        rows3.append((ts, t3[k], unc, cfg_t, masks, fa))
+    w3 = eng.edit_segments(xts, zs, rows3)
+    for k in range(2):
+        assert _rel(w3[k:k + 1], eng.edit_segments(xts, zs, [rows3[k]])) < 1e-4
+
+
+# ------------------------------------------------------------------------------------------------ the CLIs
+def test_cli_parses_the_grid_and_refuses_malformed_vectors(capsys):
+    a = main_run_segments.parse_args(["--target_prompt", "a guitar", "a violin", "--cutoff_points", "0.4", "--tstart", "100",
+                                      "60", "--tstart", "80", "80", "--cfg_tar", "12", "9", "--fix_alpha", "0.1", "0.2",
+                                      "--allow_synthetic", "--schedule", "batched", "--resampler", "sinc"])
+    assert a.tstart == [[100, 60], [80, 80]] and a.cfg_tar == [[12.0, 9.0]] and a.fix_alpha == [0.1, 0.2]
+    assert a.allow_synthetic and a.schedule == "batched" and a.resampler == "sinc" and len(a.edits) == 4
+    assert [(e["tstart"], e["fix_alpha"]) for e in a.edits] == [([100, 60], 0.1), ([100, 60], 0.2), ([80, 80], 0.1),
+                                                                ([80, 80], 0.2)]
+    assert all(e["prompts"] == ["a guitar", "a violin"] and e["cutoff_points"] == [0.4] and e["neg_prompts"] == [""]
+               for e in a.edits)
+    d = main_run_segments.parse_args(["--target_prompt", "a", "b", "c"])
+    assert d.edits == [dict(prompts=["a", "b", "c"], neg_prompts=[""], tstart=[100] * 3, cfg_scales=[12.0] * 3,
+                            cutoff_points=None, fix_alpha=0.1)]
+    recs = segments.segment_records(a.edits)
+    assert recs[1]["file"] == "001_a_guitar_a_violin_t100-60_cfg12-9_fa0.2.wav" and len({r["file"] for r in recs}) == 4
+    for argv, what in (([], "--target_prompt"),
+                       (["--target_prompt", "a", "b", "--tstart", "100"], "--tstart [100]: 1 values for 2 target prompts"),
+                       (["--target_prompt", "a", "b", "--cfg_tar", "1", "2", "3"], "3 values for 2 target prompts"),
+                       (["--target_prompt", "a", "b", "--tstart", "100", "201"], "--tstart [201] outside [1,"),
+                       (["--target_prompt", "a", "b", "--cutoff_points", "0.2", "0.5"], "--cutoff_points"),
+                       (["--target_prompt", "a", "b", "--cutoff_points", "1.5"], "--cutoff_points"),
+                       (["--target_prompt", *"abcdefghi"], "9 target prompts"),
+                       (["--target_prompt", "a", "--model_id", "stabilityai/stable-audio-open-1.0"], "Stable Audio")):
+        with pytest.raises(SystemExit):
+            main_run_segments.parse_args(argv)
+        assert what in capsys.readouterr().err, argv
+    with pytest.raises(SystemExit):
+        main_run.main(["--segment_loop", "fast"])
+    assert "--segment_loop" in capsys.readouterr().err
+
+
+def test_cli_writes_one_wav_per_row_and_segments_json(cpu_loops, monkeypatch, tmp_path, capsys):
+    m = _model()
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    monkeypatch.setattr(main_run_segments, "load_model", lambda *a, **k: m)
+    g = torch.Generator().manual_seed(3)
+    monkeypatch.setattr(main_run_segments, "load_audio",
+                        lambda *a, **k: (torch.randn(1, 1, 4 * LH, 64, generator=g) - 5.0, 16000, 0.32))
+    out = str(tmp_path / "res")
+    main_run_segments.main(["--model_id", "tiny/audioldm2", "--target_prompt", "jazz", "rock", "--tstart", "4", "3",
+                            "--tstart", "3", "3", "--cfg_tar", "9", "6", "--fix_alpha", "0.2", "--num_diffusion_steps", str(T),
+                            "--source_prompt", "rain", "--results_path", out, "-s", "2"])
+    assert "2 segment edits" in capsys.readouterr().out
+    blob = json.load(open(os.path.join(out, "segments.json")))
+    assert blob["num_diffusion_steps"] == T and blob["source_prompt"] == ["rain"] and blob["model_id"] == "tiny/audioldm2"
+    assert [r["tstart"] for r in blob["segments"]] == [[4, 3], [3, 3]]
+    assert blob["segments"][0] == dict(index=0, target_prompt=["jazz", "rock"], target_neg_prompt="", tstart=[4, 3],
+                                       cfg_tar=[9.0, 6.0], cutoff_points=None, fix_alpha=0.2,
+                                       file="000_jazz_rock_t4-3_cfg9-6_fa0.2.wav")
+    assert sorted(os.listdir(out)) == sorted([r["file"] for r in blob["segments"]] + ["segments.json"])
