@@ -32,6 +32,10 @@ OP_PC_PROBE, OP_PC_JACOBIAN, OP_PC_ORTHONORMALISE = 31, 32, 33
 OP_SA_STEP_VARIANTS = 34
 # the step of rows of P-prompt segment edits (csrc/elementwise.hip); tape.step_segments names its record itself
 OP_REVERSE_STEP_SEGMENTS = 35
+# the T5 encoder's ops beside the GEMMs (csrc/t5.hip); tape.t5_embed / rmsnorm / t5_attention / gated_act name their records
+OP_T5_EMBED, OP_RMSNORM, OP_T5_ATTENTION, OP_GATED_ACT = 36, 37, 38, 39
+T5_ATTN_HEAD_SIZES = (8, 16, 32, 64)    # head sizes AED_OP_T5_ATTENTION takes
+T5_ATTN_MAX_L = 512                     # its longest sequence
 SEG_MAX_P = 8               # prompts per row AED_OP_REVERSE_STEP_SEGMENTS takes
 PC_TAB_STRIDE = 4           # floats per slot of the ops' table: sqrt(abar_t), c0, c1, sigma_t^2 / const
 PC_MAX_EV = 8               # directions AED_OP_PC_ORTHONORMALISE takes

@@ -60,6 +60,10 @@ int launch_snake(const aed_op* op, hipStream_t s);
 int launch_sa_step(const aed_op* op, hipStream_t s);
 int launch_sa_step_variants(const aed_op* op, hipStream_t s);
 int launch_gauss_sample(const aed_op* op, hipStream_t s);
+int launch_t5_embed(const aed_op* op, hipStream_t s);
+int launch_rmsnorm(const aed_op* op, hipStream_t s);
+int launch_t5_attention(const aed_op* op, hipStream_t s);
+int launch_gated_act(const aed_op* op, hipStream_t s);
 
 int aed_num_cus();
 

@@ -61,6 +61,7 @@ static launcher_t g_table[AED_OP_COUNT] = {
     launch_rotary, launch_snake, launch_sa_step, launch_gauss_sample, launch_reverse_step_variants,
     launch_drift_step_variants, launch_reverse_step_rows, launch_pc_probe, launch_pc_jacobian, launch_pc_orthonormalise,
     launch_sa_step_variants, launch_reverse_step_segments,
+    launch_t5_embed, launch_rmsnorm, launch_t5_attention, launch_gated_act,
 };
 
 extern "C" {

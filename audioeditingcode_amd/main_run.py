@@ -67,7 +67,7 @@ def edit_clip(ldm_stable, x0, source_prompt, target_prompt, target_neg_prompt, c
     return audio, orig_audio, w_edit
 
 
-def main(argv=None):
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--device_num", type=int, default=0)
     p.add_argument("-s", "--seed", type=int, default=None)
@@ -91,15 +91,24 @@ def main(argv=None):
     p.add_argument("--allow_synthetic", action="store_true",
                    help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
                         "(benchmarking only: the output is noise)")
+    p.add_argument("--text_t5", default="torch", choices=["torch", "native"],
+                   help="T5 text encoder: torch = transformers.T5EncoderModel, native = the encoder stack on the op tape "
+                        "(HIP kernels, one hipGraph per prompt batch shape); no effect with stand-in conditioning")
     p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
                    help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
                         "torchaudio's default resampler (HIP kernel)")
     args = p.parse_args(argv)
     args.eta = 1.0
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     set_reproducability(args.seed, extreme=False)
     device = f"cuda:{args.device_num}"
     torch.cuda.set_device(args.device_num)
-    ldm_stable = load_model(args.model_id, device, args.num_diffusion_steps, allow_synthetic=args.allow_synthetic or None)
+    ldm_stable = load_model(args.model_id, device, args.num_diffusion_steps, allow_synthetic=args.allow_synthetic or None,
+                            text_t5=args.text_t5)
     src = args.init_aud if args.init_aud else (synthetic_clip(), 16000)
     sa = "stable-audio" in args.model_id
     method = None if args.resampler == "auto" else args.resampler

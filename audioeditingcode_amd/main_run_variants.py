@@ -37,6 +37,9 @@ def parse_args(argv=None):
     p.add_argument("--allow_synthetic", action="store_true",
                    help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
                         "(benchmarking only: the output is noise)")
+    p.add_argument("--text_t5", default="torch", choices=["torch", "native"],
+                   help="T5 text encoder: torch = transformers.T5EncoderModel, native = the encoder stack on the op tape "
+                        "(HIP kernels, one hipGraph per prompt batch shape); no effect with stand-in conditioning")
     p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
                    help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
                         "torchaudio's default resampler (HIP kernel)")
@@ -59,7 +62,8 @@ def main(argv=None):
     device = f"cuda:{args.device_num}"
     torch.cuda.set_device(args.device_num)
     T = args.num_diffusion_steps
-    model = load_model(args.model_id, device, T, allow_synthetic=args.allow_synthetic or None)
+    model = load_model(args.model_id, device, T, allow_synthetic=args.allow_synthetic or None,
+                       text_t5=args.text_t5)
     src = args.init_aud if args.init_aud else (synthetic_clip(), 16000)
     method = None if args.resampler == "auto" else args.resampler
     x0, sr, duration = load_audio(src, model.get_fn_STFT(), device=device, stft=True, model_sr=model.get_sr(),

@@ -94,7 +94,7 @@ class PipelineWrapper(torch.nn.Module):
 
     def __init__(self, model_id: str, device: torch.device, double_precision: bool = False,
                  token: Optional[str] = None, seed: int = 0, state_dicts: Optional[Dict] = None,
-                 allow_synthetic: Optional[bool] = None, *args, **kwargs) -> None:
+                 allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None, *args, **kwargs) -> None:
         super().__init__()
         self._init_common(model_id, device, double_precision, token, allow_synthetic)
         self.family = configs.get_family(model_id)
@@ -113,8 +113,8 @@ class PipelineWrapper(torch.nn.Module):
             self.weights_source = ckpt
             try:
                 from .text_encoders import TextEncoders
-                self.text_encoders = TextEncoders.from_pretrained(ckpt, self.kind, device=self.device)
-                self.conditioning_source = f"transformers text encoders from {ckpt}"
+                self.text_encoders = TextEncoders.from_pretrained(ckpt, self.kind, device=self.device, t5=text_t5 or "torch")
+                self.conditioning_source = f"transformers text encoders from {ckpt}" + self._t5_note(text_t5)
             except (FileNotFoundError, OSError, ImportError) as e:
                 if not self.synthetic_ok:
                     raise L.AedError(f"{ckpt}: U-Net/VAE/vocoder weights were found but the text-conditioning "
@@ -162,6 +162,13 @@ class PipelineWrapper(torch.nn.Module):
         self.token = token
         self._require_device()
         L.lib()                                                       # fail loudly if libaed.so is missing
+
+    def _t5_note(self, text_t5) -> str:
+        """What `conditioning_source` says about the T5 encoder when the native one was asked for."""
+        if (text_t5 or "torch") != "native":
+            return ""
+        return " (T5 encoder: native op tape)" if self.kind in ("tango", "audioldm2", "stable_audio") else \
+            " (no T5 encoder in this family: --text_t5 native has no effect)"
 
     def _require_device(self) -> None:
         """The product runs on HIP only.  (The CPU test suite subclasses the wrapper and overrides this hook to execute
@@ -545,7 +552,7 @@ class StableAudWrapper(PipelineWrapper):
 
     def __init__(self, model_id: str, device: torch.device, double_precision: bool = False,
                  token: Optional[str] = None, seed: int = 0, state_dicts: Optional[Dict] = None,
-                 allow_synthetic: Optional[bool] = None, *args, **kwargs) -> None:
+                 allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None, *args, **kwargs) -> None:
         torch.nn.Module.__init__(self)
         self._init_common(model_id, device, double_precision, token, allow_synthetic)
         self.family = configs.get_family(model_id)
@@ -565,8 +572,9 @@ class StableAudWrapper(PipelineWrapper):
             self.weights_source = ckpt
             try:
                 from .text_encoders import TextEncoders
-                self.text_encoders = TextEncoders.from_pretrained(ckpt, "stable_audio", device=self.device)
-                self.conditioning_source = f"transformers text encoder from {ckpt}"
+                self.text_encoders = TextEncoders.from_pretrained(ckpt, "stable_audio", device=self.device,
+                                                                  t5=text_t5 or "torch")
+                self.conditioning_source = f"transformers text encoder from {ckpt}" + self._t5_note(text_t5)
             except (FileNotFoundError, OSError, ImportError) as e:
                 if not self.synthetic_ok:
                     raise L.AedError(f"{ckpt}: DiT/VAE weights were found but the text-conditioning components could "
@@ -814,14 +822,18 @@ class StableAudWrapper(PipelineWrapper):
 
 def load_model(model_id: str, device: torch.device, num_diffusion_steps: int, double_precision: bool = False,
                token: Optional[str] = None, seed: int = 0, state_dicts: Optional[Dict] = None,
-               allow_synthetic: Optional[bool] = None) -> PipelineWrapper:
+               allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None) -> PipelineWrapper:
     """Substring dispatch + scheduler setup of models.py:1357-1374.  `allow_synthetic`: opt-in to seeded-random weights
-    and stand-in text embeddings when no checkpoint is on disk (benchmarks / tests; see PipelineWrapper.__init__)."""
+    and stand-in text embeddings when no checkpoint is on disk (benchmarks / tests; see PipelineWrapper.__init__).
+    `text_t5`: "torch" (default) or "native" -- which T5 encoder `TextEncoders.from_pretrained` loads for the families that
+    have one (TANGO, Stable Audio, AudioLDM2's second encoder); no effect on stand-in conditioning."""
+    if text_t5 not in (None, "torch", "native"):
+        raise ValueError(f"text_t5={text_t5!r}: expected 'torch' or 'native'")
     fam = configs.family_of(model_id)
     cls = {"tango": TangoWrapper, "audioldm2": AudioLDM2Wrapper, "audioldm": AudioLDMWrapper,
            "stable_audio": StableAudWrapper}[fam]
     ldm_stable = cls(model_id=model_id, device=device, double_precision=double_precision, token=token, seed=seed,
-                     state_dicts=state_dicts, allow_synthetic=allow_synthetic)
+                     state_dicts=state_dicts, allow_synthetic=allow_synthetic, text_t5=text_t5)
     ldm_stable.load_scheduler()
     ldm_stable.model.scheduler.set_timesteps(num_diffusion_steps, device=None)
     torch.cuda.empty_cache()

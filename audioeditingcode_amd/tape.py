@@ -615,6 +615,38 @@ class Tape:
                   name=name, nbytes=16 * rows * C)
         return out
 
+    # ------------------------------------------------------------------ T5 encoder ops (csrc/t5.hip)
+    def t5_embed(self, table, ids, out, *, rows, width, vocab, ldo=None, name="t5_embed"):
+        """out[r, :width] = table[ids[r], :] (AED_OP_T5_EMBED); ids a device int32[rows] the caller has range-checked."""
+        ldo = out.stride(-2) if ldo is None else ldo
+        self._add(L.OP_T5_EMBED, [rows & 0xFFFFFFFF, rows >> 32, width, vocab, ldo], [], [table, ids, out], name=name,
+                  nbytes=8 * rows * width)
+        return out
+
+    def rmsnorm(self, x, w, out, *, rows, width, eps, ldx=None, ldy=None, name="rmsnorm"):
+        """T5LayerNorm over rows of x[rows, ldx]: out = x * rsqrt(mean(x^2, -1) + eps) * w (AED_OP_RMSNORM)."""
+        ldx = x.stride(-2) if ldx is None else ldx
+        ldy = out.stride(-2) if ldy is None else ldy
+        self._add(L.OP_RMSNORM, [rows & 0xFFFFFFFF, rows >> 32, width, ldx, ldy], [eps], [x, w, out], name=name,
+                  nbytes=8 * rows * width)
+        return out
+
+    def t5_attention(self, q, k, v, pos, keymask, out, *, B, H, N, D, ldq, ldk, ldv, ldo, name="t5_attn"):
+        """softmax(q k^T + pos[h][j - i + N - 1] + keymask[b][j]) v without a 1/sqrt(D) scale (AED_OP_T5_ATTENTION) over
+        sequences of N tokens: q, k, v are column views of a fused projection buffer [B*N, ld], pos a device float[H, 2N-1],
+        keymask a device int32[B, N] or None."""
+        self._add(L.OP_T5_ATTENTION, [B, H, N, D, ldq, ldk, ldv, ldo], [], [q, k, v, pos, keymask, out], name=name,
+                  flops=4 * B * H * N * N * D, nbytes=16 * B * H * N * D)
+        return out
+
+    def gated_act(self, x, out, *, rows, F, ld_in=None, ld_out=None, name="gated_act"):
+        """out[r, c] = gelu_new(x[r, c]) * x[r, F + c] over the fused wi_0|wi_1 output x[rows, >= 2F] (AED_OP_GATED_ACT)."""
+        ld_in = x.stride(-2) if ld_in is None else ld_in
+        ld_out = out.stride(-2) if ld_out is None else ld_out
+        self._add(L.OP_GATED_ACT, [rows & 0xFFFFFFFF, rows >> 32, F, ld_in, ld_out], [], [x, out], name=name,
+                  nbytes=12 * rows * F)
+        return out
+
     def reflect_pad(self, src, dst, *, B, N, pad, ldd, name="reflect_pad"):
         self._add(L.OP_REFLECT_PAD, [B, N, pad, ldd], [], [src, dst], name=name, nbytes=8 * B * N)
 

@@ -130,10 +130,20 @@ class TextEncoders:
 
     # ------------------------------------------------------------------ loading
     @classmethod
-    def from_pretrained(cls, root: str, kind: str, device="cpu"):
+    def from_pretrained(cls, root: str, kind: str, device="cpu", t5="torch"):
         """Load from a diffusers-style snapshot directory (tokenizer/, text_encoder/, tokenizer_2/, text_encoder_2/,
-        language_model/, projection_model/).  Raises if a required sub-directory is missing."""
+        language_model/, projection_model/).  Raises if a required sub-directory is missing.  t5="native" puts a
+        `t5.NativeT5Encoder` (the encoder stack on the op tape) where the T5 module goes; everything else stays."""
         from transformers import AutoTokenizer
+        if t5 not in ("torch", "native"):
+            raise ValueError(f"t5={t5!r}: expected 'torch' or 'native'")
+
+        def load_t5(path):
+            if t5 == "native":
+                from .t5 import NativeT5Encoder
+                return NativeT5Encoder.from_pretrained(path, device)
+            from transformers import T5EncoderModel
+            return T5EncoderModel.from_pretrained(path).to(device)
 
         def need(sub):
             p = os.path.join(root, sub)
@@ -145,11 +155,8 @@ class TextEncoders:
             return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")),
                        ClapTextModelWithProjection.from_pretrained(need("text_encoder")).to(device), source=root)
         if kind == "tango":
-            from transformers import T5EncoderModel
-            return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")),
-                       T5EncoderModel.from_pretrained(need("text_encoder")).to(device), source=root)
+            return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")), load_t5(need("text_encoder")), source=root)
         if kind == "stable_audio":
-            from transformers import T5EncoderModel
             proj_dir = need("projection_model")
             with open(os.path.join(proj_dir, "config.json")) as f:
                 pc = json.load(f)
@@ -161,10 +168,9 @@ class TextEncoders:
             else:
                 proj.load_diffusers_state_dict(torch.load(os.path.join(proj_dir, "diffusion_pytorch_model.bin"),
                                                           map_location="cpu", weights_only=True))
-            return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")),
-                       T5EncoderModel.from_pretrained(need("text_encoder")).to(device),
+            return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")), load_t5(need("text_encoder")),
                        projection_model=proj.to(device), source=root)
-        from transformers import ClapModel, GPT2Model, T5EncoderModel
+        from transformers import ClapModel, GPT2Model
         proj_dir = need("projection_model")
         with open(os.path.join(proj_dir, "config.json")) as f:
             pc = json.load(f)
@@ -181,7 +187,7 @@ class TextEncoders:
         return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")),
                    ClapModel.from_pretrained(need("text_encoder")).to(device),
                    AutoTokenizer.from_pretrained(need("tokenizer_2")),
-                   T5EncoderModel.from_pretrained(need("text_encoder_2")).to(device), lm, proj.to(device),
+                   load_t5(need("text_encoder_2")), lm, proj.to(device),
                    max_new_tokens=getattr(lm.config, "max_new_tokens", None) or 8, source=root)
 
     # ------------------------------------------------------------------ helpers

@@ -149,6 +149,35 @@ enum aed_opcode {
                                  (nullable) p7=mask [K][P][numel] p8=alpha float[K] p9=traj [Z][numel]; i0,i1=numel lo/hi i2=a
                                  i3=Z (rows of p1 and p9, read at Z - step - 1; 0: both are explicit rows, without p6 only)
                                  i4=s_imm i5=v_pred i6=has_noise i7=s_mul i8=s_off i9=P; f1..f5=c0..c4 (when p5 is null)     */
+    /* 36-39: what the T5 encoder stack needs beside the GEMMs (csrc/t5.hip; audioeditingcode_amd/t5.py builds the tape).  fp32,
+       no atomics, every sum in a fixed order: a launch is bit-repeatable.  Row counts are 64-bit (lo/hi), buffers and row
+       strides are multiples of 4 floats and 16-byte aligned (whole rows move as 16-byte accesses).                          */
+    AED_OP_T5_EMBED = 36,     /* out[r][:] = table[ids[r]][:], whole rows.  The host range-checks the ids before upload (an id
+                                 outside [0, vocab) writes a zero row and reads nothing).
+                                 slots: p0=table [vocab][width] p1=ids int32[rows] p2=out [rows][ldo]; i0,i1=rows lo/hi
+                                 i2=width (multiple of 4) i3=vocab i4=ldo.  Refused: null pointers, rows < 1, vocab < 1, a width
+                                 or ldo that is no multiple of 4, ldo < width, unaligned table / out                          */
+    AED_OP_RMSNORM = 37,      /* T5LayerNorm: y = x * (1 / sqrt(mean(x^2 over the row) + eps)) * w -- no mean subtraction, no
+                                 bias; one wave per row.  (The residual additions ride in the neighbouring GEMMs' epilogue.)
+                                 slots: p0=x [rows][ldx] p1=w [width] p2=y [rows][ldy] (may be x); i0,i1=rows lo/hi i2=width
+                                 i3=ldx i4=ldy; f0=eps.  Refused: null pointers, rows < 1, a width that is no multiple of 32 in
+                                 [32, 4096], strides below the width or no multiple of 4, eps < 0, unaligned pointers         */
+    AED_OP_T5_ATTENTION = 38, /* out = softmax(q.k^T + pos[h][j - i + L - 1] + keymask[b][j]) . v per (batch item b, head h),
+                                 WITHOUT a 1/sqrt(D) scale.  q, k, v are read in place from a fused projection buffer: row
+                                 b*L + i, head h in columns [h*D, (h+1)*D) of each pointer.  pos is the relative-position bias
+                                 of every delta j - i in [-(L-1), L-1], built by the host; a masked key (keymask 0) has weight
+                                 exactly 0, a query row without an attended key gives zeros.  Keys run in tiles of 64 with a
+                                 running maximum and sum.
+                                 slots: p0=q p1=k p2=v p3=pos float[H][2L-1] p4=keymask int32[B][L] (null: no key masked)
+                                 p5=out [B*L][ldo]; i0=B i1=H i2=L i3=D i4=ldq i5=ldk i6=ldv i7=ldo.  Refused: null pointers
+                                 (p4 excepted), D outside {8, 16, 32, 64}, L outside [1, 512], B or H < 1, a stride below H*D
+                                 or no multiple of 4, unaligned q / k / v, more than 2^31 workgroups                          */
+    AED_OP_GATED_ACT = 39,    /* out[r][c] = gelu_new(in[r][c]) * in[r][F + c] over the two halves of the fused wi_0|wi_1 GEMM
+                                 output, gelu_new(x) = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))).  (The non-gated ReLU
+                                 feed-forward needs no op: AED_OP_CONV_GEMM's out_act AED_ACT_LEAKY with slope 0.)
+                                 slots: p0=in [rows][ld_in] p1=out [rows][ld_out]; i0,i1=rows lo/hi i2=F i3=ld_in i4=ld_out.
+                                 Refused: null pointers, rows < 1, an F, ld_in or ld_out that is no multiple of 4, ld_in < 2F,
+                                 ld_out < F, unaligned pointers                                                               */
     AED_OP_COUNT
 };
 
