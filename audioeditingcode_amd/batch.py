@@ -13,7 +13,7 @@ import json
 
 import torch
 
-from .ddm_inversion.inversion_utils import conditioning_from_text
+from .ddm_inversion.inversion_utils import prompt_cache
 from .variants import EditVariant, decode_variants, eta_for_engine, slug  # noqa: F401  (decode_variants: re-exported)
 
 
@@ -36,14 +36,7 @@ def inversion_reverse_clips(model, inversions, edits, etas=1.0, chunk=None):
     for c, (xts, zs) in enumerate(inversions):
         if xts.dim() != 4 or zs.dim() != 4:
             raise ValueError(f"inversion_reverse_clips: clip {c}: xts [T+1, C, H, W] and zs [Z, C, H, W] of ONE clip")
-    enc, enc_neg = {}, {}
-
-    def cond(p, neg):
-        box = enc_neg if neg else enc
-        if p not in box:
-            box[p] = conditioning_from_text(model, model.encode_text([p], negative=True) if neg
-                                            else model.encode_text([p]))
-        return box[p]
+    cond = prompt_cache(model)                      # every distinct prompt is encoded once
     by_shape = {}
     for k, (c, _) in enumerate(edits):
         by_shape.setdefault(tuple(inversions[c][0].shape[1:]), []).append(k)

@@ -66,6 +66,22 @@ def conditioning_from_text(model, triple):
     return Conditioning(ehs0=hs, mask0=mask)
 
 
+def prompt_cache(model, wrap=None):
+    """cond(prompt, negative=False): the text encoding of a prompt, computed at the first request and kept for the life of
+    the returned callable.  A batched wrapper makes one per call, so every distinct (prompt, negative?) pair of its rows is
+    encoded once, in the order the rows first ask (stand-in conditioning is seeded, so the order matters).
+    wrap(hidden_states, class_labels, mask) shapes encode_text's triple; default: the loop engine's Conditioning."""
+    wrap = wrap or (lambda *triple: conditioning_from_text(model, triple))
+    enc, enc_neg = {}, {}
+
+    def cond(p, negative=False):
+        box = enc_neg if negative else enc
+        if p not in box:
+            box[p] = wrap(*(model.encode_text([p], negative=True) if negative else model.encode_text([p])))
+        return box[p]
+    return cond
+
+
 def inversion_forward_process(model, x0: torch.Tensor, etas: Optional[float] = None, prog_bar: bool = False,
                               prompts: List[str] = [""], cfg_scales: List[float] = [3.5],
                               num_inference_steps: int = 50, cutoff_points: Optional[List[float]] = None,

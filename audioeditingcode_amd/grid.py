@@ -13,7 +13,7 @@ import itertools
 
 import torch
 
-from .ddm_inversion.inversion_utils import conditioning_from_text, inversion_forward_process
+from .ddm_inversion.inversion_utils import conditioning_from_text, inversion_forward_process, prompt_cache
 from .variants import decode_variants, eta_for_engine, slug  # noqa: F401  (decode_variants: re-exported)
 
 METHODS = ("ours", "sdedit", "ddim")
@@ -166,14 +166,7 @@ def run_grid(model, clips, rows, cfg_src=3.0, etas=1.0, chunk=None, prepared=Non
     T = sched.num_inference_steps
     check_grid(len(clips), rows, T, etas)
     prep = prepared if prepared is not None else prepare_grid(model, clips, rows, cfg_src, etas, chunk)
-    enc, enc_neg = {}, {}
-
-    def cond(p, neg=False):
-        box = enc_neg if neg else enc
-        if p not in box:
-            box[p] = conditioning_from_text(model, model.encode_text([p], negative=True) if neg
-                                            else model.encode_text([p]))
-        return box[p]
+    cond = prompt_cache(model)                      # every distinct prompt is encoded once
     by_shape = {}
     for k, (c, _) in enumerate(rows):
         by_shape.setdefault(tuple(clips[c][0].shape[1:]), []).append(k)

@@ -13,6 +13,8 @@ from typing import List, Optional
 
 import torch
 
+from .cli import add_options, open_model, provenance, vocode
+
 
 def _default_fns():
     from . import pc_drift
@@ -113,8 +115,7 @@ def output_name(args, ex, ev=None) -> str:
 
 def build_parser():
     p = argparse.ArgumentParser("Apply extracted PCs to audio")
-    p.add_argument("--device_num", type=int, default=0)
-    p.add_argument("-s", "--seed", type=int, default=None)
+    add_options(p, "device")
     p.add_argument("--extraction_path", type=str, required=True)
     p.add_argument("--drift_start", type=int, required=True)
     p.add_argument("--drift_end", type=int, required=True)
@@ -126,38 +127,28 @@ def build_parser():
     p.add_argument("--combine_evs", action="store_true")
     p.add_argument("--evals_pt", type=str, default=None)
     p.add_argument("--rand_v", action="store_true")
-    p.add_argument("--allow_synthetic", action="store_true",
-                   help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
-                        "(benchmarking only: the output is noise)")
+    add_options(p, "synthetic")
     return p
 
 
 def main(argv: Optional[List[str]] = None):
-    from .models import load_model
-    from .utils import set_reproducability, write_wav
+    from .utils import write_wav
     args = build_parser().parse_args(argv)
     args.shift_x0_for_np = True
     args.sub_iters = None
     if args.drift_start < args.drift_end:
         raise ValueError("Drift start must be greater than drift end")
-    set_reproducability(args.seed, extreme=False)
     path = args.extraction_path[:-3] if args.extraction_path.endswith(".pt") else args.extraction_path
-    device = f"cuda:{args.device_num}"
-    torch.cuda.set_device(args.device_num)
-    load_dict = torch.load(path + ".pt", map_location=device, weights_only=False)
+    load_dict = torch.load(path + ".pt", map_location=f"cuda:{args.device_num}", weights_only=False)
     ex = load_dict["args"]
     if args.evals_pt is not None:
         args.evals_pt = torch.load(args.evals_pt, weights_only=False)
-    ldm_stable = load_model(ex.model_id, device, ex.num_diffusion_steps, ex.double_precision,
-                            allow_synthetic=getattr(args, "allow_synthetic", False) or None)
-    print(f"weights: {ldm_stable.weights_source}; text conditioning: {ldm_stable.conditioning_source}")
+    ldm_stable, device = open_model(args.seed, args.device_num, ex.model_id, ex.num_diffusion_steps, ex.double_precision,
+                                    allow_synthetic=args.allow_synthetic)
+    print(provenance(ldm_stable))
     t0 = time.time()
     xt = apply_pcs(ldm_stable, load_dict, args, device)
-    with torch.inference_mode():
-        x0_dec = torch.cat([ldm_stable.vae_decode(xt[i].unsqueeze(0)) for i in range(len(xt))], dim=0)
-        if x0_dec.dim() < 4:
-            x0_dec = x0_dec[None]
-        audio = ldm_stable.decode_to_mel(x0_dec)
+    audio = vocode(ldm_stable, xt, one_by_one=True)
     out_dir = path + "_driftgens"
     os.makedirs(out_dir, exist_ok=True)
     if args.combine_evs:

@@ -6,7 +6,6 @@ One variant per drift window x amount x PC (with --combine_evs: per window x amo
 --drift_end are paired lists.  The other flags are main_pc_apply_drift's.  Writes one wav per variant, named as
 main_pc_apply_drift names it, and drift_grid.json (index, evs, amount, window, file) next to them."""
 import argparse
-import json
 import os
 import time
 from types import SimpleNamespace
@@ -14,14 +13,14 @@ from typing import List, Optional
 
 import torch
 
+from .cli import add_options, open_model, provenance, vocode, write_rows
 from .drift_grid import apply_pcs_grid, expand_grid
 from .main_pc_apply_drift import output_name
 
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    p.add_argument("--device_num", type=int, default=0)
-    p.add_argument("-s", "--seed", type=int, default=None)
+    add_options(p, "device")
     p.add_argument("--extraction_path", type=str, required=True)
     p.add_argument("--drift_start", type=int, nargs="+", required=True)
     p.add_argument("--drift_end", type=int, nargs="+", required=True)
@@ -33,9 +32,7 @@ def parse_args(argv=None):
     p.add_argument("--combine_evs", action="store_true")
     p.add_argument("--evals_pt", type=str, default=None)
     p.add_argument("--rand_v", action="store_true")
-    p.add_argument("--allow_synthetic", action="store_true",
-                   help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
-                        "(benchmarking only: the output is noise)")
+    add_options(p, "synthetic")
     args = p.parse_args(argv)
     args.shift_x0_for_np = True
     args.sub_iters = None
@@ -67,37 +64,25 @@ def records(args, ex):
 
 
 def main(argv: Optional[List[str]] = None):
-    from .models import load_model
-    from .utils import set_reproducability, write_wav
     args = parse_args(argv)
-    set_reproducability(args.seed, extreme=False)
     path = args.extraction_path[:-3] if args.extraction_path.endswith(".pt") else args.extraction_path
-    device = f"cuda:{args.device_num}"
-    torch.cuda.set_device(args.device_num)
-    load_dict = torch.load(path + ".pt", map_location=device, weights_only=False)
+    load_dict = torch.load(path + ".pt", map_location=f"cuda:{args.device_num}", weights_only=False)
     ex = load_dict["args"]
     evals = torch.load(args.evals_pt, weights_only=False) if args.evals_pt is not None else None
-    ldm_stable = load_model(ex.model_id, device, ex.num_diffusion_steps, ex.double_precision,
-                            allow_synthetic=args.allow_synthetic or None)
-    print(f"weights: {ldm_stable.weights_source}; text conditioning: {ldm_stable.conditioning_source}")
+    ldm_stable, _ = open_model(args.seed, args.device_num, ex.model_id, ex.num_diffusion_steps, ex.double_precision,
+                               allow_synthetic=args.allow_synthetic)
+    print(provenance(ldm_stable))
     t0 = time.time()
     xt = apply_pcs_grid(ldm_stable, load_dict, args.variants, fix_alpha=args.fix_alpha, fade_length=args.fade_length,
                         use_specific_ts_pc=args.use_specific_ts_pc, evals_pt=evals, rand_v=args.rand_v,
                         shift_x0_for_np=args.shift_x0_for_np)
-    with torch.inference_mode():
-        x0_dec = torch.cat([ldm_stable.vae_decode(xt[i].unsqueeze(0)) for i in range(len(xt))], dim=0)
-        if x0_dec.dim() < 4:
-            x0_dec = x0_dec[None]
-        audio = ldm_stable.decode_to_mel(x0_dec)
+    audio = vocode(ldm_stable, xt, one_by_one=True)
     out_dir = path + "_driftgens"
-    os.makedirs(out_dir, exist_ok=True)
     recs = records(args, ex)
-    for rec, wav in zip(recs, audio):
-        write_wav(os.path.join(out_dir, rec["file"]), wav.numpy())
-    with open(os.path.join(out_dir, "drift_grid.json"), "w") as f:
-        json.dump(dict(extraction=os.path.basename(path) + ".pt", fix_alpha=args.fix_alpha, fade_length=args.fade_length,
-                       use_specific_ts_pc=args.use_specific_ts_pc, rand_v=args.rand_v,
-                       avg_evals=args.evals_pt is not None, variants=recs), f, indent=1)
+    write_rows(out_dir, recs, audio, 16000, "drift_grid.json",
+               dict(extraction=os.path.basename(path) + ".pt", fix_alpha=args.fix_alpha, fade_length=args.fade_length,
+                    use_specific_ts_pc=args.use_specific_ts_pc, rand_v=args.rand_v, avg_evals=args.evals_pt is not None,
+                    variants=recs))
     print(f"applied {len(recs)} drift variants in {time.time() - t0:.1f} s -> {out_dir}")
 
 

@@ -20,6 +20,8 @@ from typing import List, Optional
 
 import torch
 
+from .cli import add_options, load_clip, open_model, prompt_dir, provenance, vocode
+
 
 def _default_fns():
     from . import pc_drift
@@ -146,18 +148,15 @@ def save_extraction(ckpt: dict, path: str):
 
 def build_parser():
     p = argparse.ArgumentParser(description="Extract PCs for a real audio signal")
-    p.add_argument("--device_num", type=int, default=0)
-    p.add_argument("-s", "--seed", type=int, default=None)
+    add_options(p, "device")
     p.add_argument("--cfg_tar", type=float, default=3)
-    p.add_argument("--model_id", type=str, default="cvssp/audioldm2-music")
-    p.add_argument("--init_aud", type=str, default=None, help="wav to invert (default: the synthetic benchmark clip)")
-    p.add_argument("--num_diffusion_steps", type=int, default=200)
+    add_options(p, "model", "clip", "steps", init_aud_help="wav to invert (default: the synthetic benchmark clip)")
     p.add_argument("--source_prompt", type=str, nargs="+", default=[""])
     p.add_argument("--target_neg_prompt", type=str, nargs="+", default=[""])
     p.add_argument("--corr_to_swap", type=float, default=0.8)
     p.add_argument("--drift_start", type=int, default=None)
     p.add_argument("--drift_end", type=int, default=None)
-    p.add_argument("--results_path", default="pc_extractions")
+    add_options(p, "results", results_path="pc_extractions")
     p.add_argument("-c", "--const", type=float, default=1e-3)
     p.add_argument("--n_evs", type=int, default=1)
     p.add_argument("-p", "--patch", nargs=2, default=None, type=int)
@@ -165,12 +164,7 @@ def build_parser():
     p.add_argument("-d", "--dry", action="store_true")
     p.add_argument("--timestep_group", type=int, default=1,
                    help="window timesteps per batched subspace iteration (1: one timestep at a time, the reference's order)")
-    p.add_argument("--allow_synthetic", action="store_true",
-                   help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
-                        "(benchmarking only: the output is noise)")
-    p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
-                   help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
-                        "torchaudio's default resampler (HIP kernel)")
+    add_options(p, "synthetic", "resampler")
     return p
 
 
@@ -185,42 +179,25 @@ def finish_args(args):
 
 
 def main(argv: Optional[List[str]] = None):
-    from .models import load_model
-    from .utils import load_audio, resampler_label, set_reproducability, synthetic_clip, write_wav
+    from .utils import write_wav
     parser = build_parser()
     args = finish_args(parser.parse_args(argv))
     if args.timestep_group < 1:
         parser.error(f"--timestep_group {args.timestep_group} < 1")
-    set_reproducability(args.seed, extreme=False)
-    device = f"cuda:{args.device_num}"
-    torch.cuda.set_device(args.device_num)
-    ldm_stable = load_model(args.model_id, device, args.num_diffusion_steps, args.double_precision,
-                            allow_synthetic=getattr(args, "allow_synthetic", False) or None)
-    src = args.init_aud if args.init_aud else (synthetic_clip(), 16000)
-    method = None if getattr(args, "resampler", "auto") == "auto" else args.resampler
-    print(f"weights: {ldm_stable.weights_source}; text conditioning: {ldm_stable.conditioning_source}; "
-          f"resampler: {resampler_label(src, 16000, method)}")
+    ldm_stable, device = open_model(args.seed, args.device_num, args.model_id, args.num_diffusion_steps,
+                                    args.double_precision, allow_synthetic=args.allow_synthetic)
     # (the reference's call site is stale here -- no stft=True, 3-tuple bound to x0, main_pc_extract_inv.py:110; SURVEY
     # quirk 10 -- the evident intent is implemented)
-    x0, _, _ = load_audio(src, ldm_stable.get_fn_STFT(), device=device, stft=True, model_sr=ldm_stable.get_sr(),
-                          resampler=method)
+    x0, _, _, label = load_clip(ldm_stable, args.init_aud, device, args.resampler, stft=True)
+    print(provenance(ldm_stable, label))
     with torch.inference_mode():
         w0 = ldm_stable.vae_encode(x0)
-    clip = os.path.basename(args.init_aud).split(".")[0] if args.init_aud else "synthetic"
-    save_path = os.path.join(args.results_path, args.model_id.split("/")[-1], clip,
-                             "pmt_" + "__".join(x.replace(" ", "_") for x in args.source_prompt) + "__neg__" +
-                             "__".join(x.replace(" ", "_") for x in args.target_neg_prompt))
-    os.makedirs(save_path, exist_ok=True)
+    save_path = prompt_dir(args.results_path, args.model_id, args.init_aud, args.source_prompt, args.target_neg_prompt)
     stem = os.path.join(save_path, extraction_name(args))
     t0 = time.time()
     ckpt = extract_pcs(ldm_stable, w0, args, checkpoint_cb=lambda st: save_extraction(st, stem))
     save_extraction(ckpt, stem)
-    with torch.inference_mode():
-        x0_dec = ldm_stable.vae_decode(ckpt["final"])
-        if x0_dec.dim() < 4:
-            x0_dec = x0_dec[None]
-        audio = ldm_stable.decode_to_mel(x0_dec)
-    write_wav(stem + ".wav", audio[0].numpy())
+    write_wav(stem + ".wav", vocode(ldm_stable, ckpt["final"])[0].numpy())
     print(f"extracted {len(ckpt['eigdata'])} timesteps x {args.n_evs} PCs in {time.time() - t0:.1f} s -> {stem}.pt")
 
 

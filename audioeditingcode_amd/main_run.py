@@ -10,10 +10,10 @@ import warnings
 
 import torch
 
+from .cli import add_options, load_clip, open_model, provenance
 from .ddm_inversion.ddim_inversion import ddim_inversion, text2image_ldm_stable
 from .ddm_inversion.inversion_utils import inversion_forward_process, inversion_reverse_process
-from .models import load_model
-from .utils import load_audio, resampler_label, set_reproducability, synthetic_clip, write_wav
+from .utils import write_wav
 
 
 def edit_clip(ldm_stable, x0, source_prompt, target_prompt, target_neg_prompt, cfg_src, cfg_tar, T, tstart,
@@ -69,34 +69,22 @@ def edit_clip(ldm_stable, x0, source_prompt, target_prompt, target_neg_prompt, c
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument("--device_num", type=int, default=0)
-    p.add_argument("-s", "--seed", type=int, default=None)
-    p.add_argument("--model_id", type=str, default="cvssp/audioldm2-music")
-    p.add_argument("--init_aud", type=str, default=None)
-    p.add_argument("--cfg_src", type=float, nargs="+", default=[3])
+    add_options(p, "device", "model", "clip", "cfg_src")
     p.add_argument("--cfg_tar", type=float, nargs="+", default=[12])
-    p.add_argument("--num_diffusion_steps", type=int, default=200)
+    add_options(p, "steps")
     p.add_argument("--target_prompt", type=str, nargs="+", default=[""])
     p.add_argument("--source_prompt", type=str, nargs="*", default=[""])
     p.add_argument("--target_neg_prompt", type=str, nargs="*", default=[""])
     p.add_argument("--tstart", type=int, nargs="+", default=[100])
-    p.add_argument("--results_path", default="results")
+    add_options(p, "results")
     p.add_argument("--mode", default="ours", choices=["ours", "ddim"])
     p.add_argument("--cutoff_points", type=float, nargs="*", default=None)
     p.add_argument("--fix_alpha", type=float, default=0.1)
-    p.add_argument("--schedule", default="sequential", choices=["sequential", "batched"])
+    add_options(p, "schedule")
     p.add_argument("--segment_loop", default="host", choices=["host", "device"],
                    help="several target prompts with unequal --tstart: host = the step-by-step loop of the reference, "
                         "device = one captured device loop with the fused step-and-blend kernel")
-    p.add_argument("--allow_synthetic", action="store_true",
-                   help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
-                        "(benchmarking only: the output is noise)")
-    p.add_argument("--text_t5", default="torch", choices=["torch", "native"],
-                   help="T5 text encoder: torch = transformers.T5EncoderModel, native = the encoder stack on the op tape "
-                        "(HIP kernels, one hipGraph per prompt batch shape); no effect with stand-in conditioning")
-    p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
-                   help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
-                        "torchaudio's default resampler (HIP kernel)")
+    add_options(p, "synthetic", "text_t5", "resampler")
     args = p.parse_args(argv)
     args.eta = 1.0
     return args
@@ -104,25 +92,17 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    set_reproducability(args.seed, extreme=False)
-    device = f"cuda:{args.device_num}"
-    torch.cuda.set_device(args.device_num)
-    ldm_stable = load_model(args.model_id, device, args.num_diffusion_steps, allow_synthetic=args.allow_synthetic or None,
-                            text_t5=args.text_t5)
-    src = args.init_aud if args.init_aud else (synthetic_clip(), 16000)
-    sa = "stable-audio" in args.model_id
-    method = None if args.resampler == "auto" else args.resampler
-    x0, sr, duration = load_audio(src, ldm_stable.get_fn_STFT(), device=device, stft=not sa, model_sr=ldm_stable.get_sr(),
-                                  resampler=method)
+    ldm_stable, device = open_model(args.seed, args.device_num, args.model_id, args.num_diffusion_steps,
+                                    allow_synthetic=args.allow_synthetic, text_t5=args.text_t5)
+    x0, sr, duration, label = load_clip(ldm_stable, args.init_aud, device, args.resampler,
+                                        stft="stable-audio" not in args.model_id)
     t0 = time.time()
     audio, orig, _ = edit_clip(ldm_stable, x0, args.source_prompt, args.target_prompt, args.target_neg_prompt,
                                args.cfg_src, args.cfg_tar, args.num_diffusion_steps, args.tstart, args.mode,
                                args.eta, args.schedule, cutoff_points=args.cutoff_points, fix_alpha=args.fix_alpha,
                                duration=duration, segment_loop=args.segment_loop)
     torch.cuda.synchronize()
-    print(f"edited {duration:.1f} s clip in {time.time() - t0:.2f} s (weights: {ldm_stable.weights_source}; "
-          f"text conditioning: {ldm_stable.conditioning_source}; "
-          f"resampler: {resampler_label(src, ldm_stable.get_sr() if sa else 16000, method)})")
+    print(f"edited {duration:.1f} s clip in {time.time() - t0:.2f} s ({provenance(ldm_stable, label)})")
     os.makedirs(args.results_path, exist_ok=True)
     # main_run.py:223-224 saves the whole [channels, n] tensor: mono for the mel families, stereo for Stable Audio
     audio, orig = (a if a.dim() == 2 else a.reshape(-1, a.shape[-1]) for a in (audio, orig))

@@ -6,41 +6,22 @@ batch.json: [{"init_aud": "a.wav", "source_prompt": "a piano",
 Writes one wav per edit and batch.json (index, clip, prompts, cfg_tar, tstart, file) to --results_path.  A clip without
 "init_aud" is a synthetic 10 s clip seeded by its position in the manifest."""
 import argparse
-import json
-import os
 import time
 
 import torch
 
 from .batch import batch_records, decode_variants, inversion_reverse_clips, parse_manifest
+from .cli import add_options, load_clip, open_model, provenance, require_family, write_rows
 from .ddm_inversion.inversion_utils import inversion_forward_process
-from .models import load_model
-from .utils import load_audio, resampler_label, set_reproducability, synthetic_clip, write_wav
 
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    p.add_argument("--device_num", type=int, default=0)
-    p.add_argument("-s", "--seed", type=int, default=None)
-    p.add_argument("--model_id", type=str, default="cvssp/audioldm2-music")
+    add_options(p, "device", "model")
     p.add_argument("--manifest", type=str, required=True, help="JSON list of {init_aud?, source_prompt?, edits: [...]}")
-    p.add_argument("--cfg_src", type=float, nargs="+", default=[3])
-    p.add_argument("--num_diffusion_steps", type=int, default=200)
-    p.add_argument("--eta", type=float, default=1.0)
-    p.add_argument("--schedule", default="sequential", choices=["sequential", "batched"])
-    p.add_argument("--results_path", default="results")
-    p.add_argument("--allow_synthetic", action="store_true",
-                   help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
-                        "(benchmarking only: the output is noise)")
-    p.add_argument("--text_t5", default="torch", choices=["torch", "native"],
-                   help="T5 text encoder: torch = transformers.T5EncoderModel, native = the encoder stack on the op tape "
-                        "(HIP kernels, one hipGraph per prompt batch shape); no effect with stand-in conditioning")
-    p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
-                   help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
-                        "torchaudio's default resampler (HIP kernel)")
+    add_options(p, "cfg_src", "steps", "eta", "schedule", "results", "synthetic", "text_t5", "resampler")
     args = p.parse_args(argv)
-    if "stable-audio" in args.model_id:
-        p.error("Stable Audio is not supported by the batched clip loop (use main_run per edit)")
+    require_family(p, args.model_id, False, "Stable Audio is not supported by the batched clip loop (use main_run per edit)")
     try:
         with open(args.manifest) as f:
             args.clips, args.edits = parse_manifest(f.read(), args.num_diffusion_steps)
@@ -51,23 +32,16 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    set_reproducability(args.seed, extreme=False)
-    device = f"cuda:{args.device_num}"
-    torch.cuda.set_device(args.device_num)
     T = args.num_diffusion_steps
-    model = load_model(args.model_id, device, T, allow_synthetic=args.allow_synthetic or None,
-                       text_t5=args.text_t5)
+    model, device = open_model(args.seed, args.device_num, args.model_id, T, allow_synthetic=args.allow_synthetic,
+                               text_t5=args.text_t5)
     t0 = time.time()
-    inversions, sr = [], None
-    method = None if args.resampler == "auto" else args.resampler
-    resamplers = []
+    inversions, labels, sr = [], [], None
     with torch.inference_mode():
         for c, clip in enumerate(args.clips):
             Z = max(v.tstart for k, v in args.edits if k == c)
-            src = clip["init_aud"] if clip["init_aud"] else (synthetic_clip(seed=1234 + c), 16000)
-            x0, sr, _ = load_audio(src, model.get_fn_STFT(), device=device, stft=True, model_sr=model.get_sr(),
-                                   resampler=method)
-            resamplers.append(resampler_label(src, 16000, method))
+            x0, sr, _, label = load_clip(model, clip["init_aud"], device, args.resampler, stft=True, seed=1234 + c)
+            labels.append(label)
             _, zs, wts, _ = inversion_forward_process(model, model.vae_encode(x0), etas=args.eta,
                                                       prompts=[clip["source_prompt"]], cfg_scales=args.cfg_src,
                                                       num_inference_steps=T, numerical_fix=True, schedule=args.schedule)
@@ -76,16 +50,11 @@ def main(argv=None):
         groups = [lat] if torch.is_tensor(lat) else [w[None] for w in lat]
         audio = [wav for g in groups for wav in decode_variants(model, g)]
     torch.cuda.synchronize()
-    print(f"{len(args.edits)} edits of {len(args.clips)} clips in {time.time() - t0:.2f} s (weights: "
-          f"{model.weights_source}; text conditioning: {model.conditioning_source}; "
-          f"resampler: {', '.join(sorted(set(resamplers)))})")
-    os.makedirs(args.results_path, exist_ok=True)
+    print(f"{len(args.edits)} edits of {len(args.clips)} clips in {time.time() - t0:.2f} s ({provenance(model, labels)})")
     records = batch_records(args.clips, args.edits)
-    for rec, wav in zip(records, audio):
-        write_wav(os.path.join(args.results_path, rec["file"]), wav.reshape(1, -1).numpy(), sr=sr)
-    with open(os.path.join(args.results_path, "batch.json"), "w") as f:
-        json.dump(dict(cfg_src=args.cfg_src, num_diffusion_steps=T, eta=args.eta, model_id=args.model_id,
-                       clips=args.clips, edits=records), f, indent=1)
+    write_rows(args.results_path, records, audio, sr, "batch.json",
+               dict(cfg_src=args.cfg_src, num_diffusion_steps=T, eta=args.eta, model_id=args.model_id, clips=args.clips,
+                    edits=records))
 
 
 if __name__ == "__main__":

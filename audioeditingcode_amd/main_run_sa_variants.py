@@ -6,50 +6,31 @@ python -m audioeditingcode_amd.main_run_sa_variants --init_aud clip.wav --source
 Writes one stereo wav per variant and variants.json (index, prompts, cfg_tar, tstart, file) to --results_path.  Without
 --init_aud a synthetic 10 s clip is edited.  The solver's noise scale is the scheduler's: there is no --eta."""
 import argparse
-import json
-import os
 import time
 
 import torch
 
+from .cli import add_options, check_tstarts, load_clip, open_model, provenance, require_family, write_rows
 from .ddm_inversion.inversion_utils import inversion_forward_process
-from .models import load_model
 from .stable_audio_variants import inversion_reverse_variants_sa
-from .utils import load_audio, resampler_label, set_reproducability, synthetic_clip, write_wav
 from .variants import expand_grid, manifest
 
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0].replace("\n", " "))
-    p.add_argument("--device_num", type=int, default=0)
-    p.add_argument("-s", "--seed", type=int, default=None)
-    p.add_argument("--model_id", type=str, default="stabilityai/stable-audio-open-1.0")
-    p.add_argument("--init_aud", type=str, default=None)
+    add_options(p, "device", "model", "clip", model_id="stabilityai/stable-audio-open-1.0")
     p.add_argument("--source_prompt", type=str, nargs="*", default=[""])
-    p.add_argument("--cfg_src", type=float, nargs="+", default=[3])
-    p.add_argument("--num_diffusion_steps", type=int, default=200)
-    p.add_argument("--schedule", default="sequential", choices=["sequential", "batched"])
+    add_options(p, "cfg_src", "steps", "schedule")
     p.add_argument("--target_prompt", type=str, nargs="+", default=[""])
     p.add_argument("--target_neg_prompt", type=str, nargs="*", default=[""],
                    help="one negative prompt for every target prompt, or one per target prompt")
     p.add_argument("--cfg_tar", type=float, nargs="+", default=[12])
     p.add_argument("--tstart", type=int, nargs="+", default=[100])
-    p.add_argument("--results_path", default="results")
-    p.add_argument("--allow_synthetic", action="store_true",
-                   help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
-                        "(benchmarking only: the output is noise)")
-    p.add_argument("--text_t5", default="torch", choices=["torch", "native"],
-                   help="T5 text encoder: torch = transformers.T5EncoderModel, native = the encoder stack on the op tape "
-                        "(HIP kernels, one hipGraph per prompt batch shape); no effect with stand-in conditioning")
-    p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
-                   help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
-                        "torchaudio's default resampler (HIP kernel)")
+    add_options(p, "results", "synthetic", "text_t5", "resampler")
     args = p.parse_args(argv)
-    if "stable-audio" not in args.model_id:
-        p.error(f"--model_id {args.model_id} is not a Stable Audio model (use main_run_variants for the mel-latent families)")
-    bad = [t for t in args.tstart if not 1 <= t <= args.num_diffusion_steps]
-    if bad:
-        p.error(f"--tstart {bad} outside [1, --num_diffusion_steps={args.num_diffusion_steps}]")
+    require_family(p, args.model_id, True, f"--model_id {args.model_id} is not a Stable Audio model (use main_run_variants "
+                                           f"for the mel-latent families)")
+    check_tstarts(p, args.tstart, args.num_diffusion_steps)
     try:
         args.variants = expand_grid(args.target_prompt, args.cfg_tar, args.tstart, args.target_neg_prompt)
     except ValueError as e:
@@ -59,16 +40,10 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    set_reproducability(args.seed, extreme=False)
-    device = f"cuda:{args.device_num}"
-    torch.cuda.set_device(args.device_num)
     T = args.num_diffusion_steps
-    model = load_model(args.model_id, device, T, allow_synthetic=args.allow_synthetic or None,
-                       text_t5=args.text_t5)
-    src = args.init_aud if args.init_aud else (synthetic_clip(), 16000)
-    method = None if args.resampler == "auto" else args.resampler
-    x0, sr, duration = load_audio(src, model.get_fn_STFT(), device=device, stft=False, model_sr=model.get_sr(),
-                                  resampler=method)
+    model, device = open_model(args.seed, args.device_num, args.model_id, T, allow_synthetic=args.allow_synthetic,
+                               text_t5=args.text_t5)
+    x0, sr, duration, label = load_clip(model, args.init_aud, device, args.resampler, stft=False)
     t0 = time.time()
     with torch.inference_mode():
         w0 = model.vae_encode(x0)
@@ -79,16 +54,11 @@ def main(argv=None):
         lat = inversion_reverse_variants_sa(model, wts, zs[:Z], args.variants, extra_info, duration=duration)
         audio = [model.vae_decode(w[None]).detach().cpu().squeeze(0) for w in lat]      # batch-1 Oobleck decodes
     torch.cuda.synchronize()
-    print(f"{len(args.variants)} edits of a {duration:.1f} s clip in {time.time() - t0:.2f} s (weights: "
-          f"{model.weights_source}; text conditioning: {model.conditioning_source}; "
-          f"resampler: {resampler_label(src, model.get_sr(), method)})")
-    os.makedirs(args.results_path, exist_ok=True)
+    print(f"{len(args.variants)} edits of a {duration:.1f} s clip in {time.time() - t0:.2f} s ({provenance(model, label)})")
     records = manifest(args.variants)
-    for rec, wav in zip(records, audio):
-        write_wav(os.path.join(args.results_path, rec["file"]), wav.reshape(-1, wav.shape[-1]).numpy(), sr=sr)
-    with open(os.path.join(args.results_path, "variants.json"), "w") as f:
-        json.dump(dict(source_prompt=args.source_prompt, cfg_src=args.cfg_src, num_diffusion_steps=T,
-                       model_id=args.model_id, variants=records), f, indent=1)
+    write_rows(args.results_path, records, audio, sr, "variants.json",
+               dict(source_prompt=args.source_prompt, cfg_src=args.cfg_src, num_diffusion_steps=T, model_id=args.model_id,
+                    variants=records))
 
 
 if __name__ == "__main__":

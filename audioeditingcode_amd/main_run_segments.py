@@ -8,30 +8,21 @@ Prompt p edits its part of the clip (split at --cutoff_points) from its own tsta
 prompts, tstart, cfg_tar, cutoff_points, fix_alpha, file) to --results_path.  Without --init_aud a synthetic 10 s clip is
 edited."""
 import argparse
-import json
-import os
 import time
 
 import torch
 
+from .cli import add_options, check_tstarts, load_clip, open_model, provenance, require_family, write_rows
 from .ddm_inversion.inversion_utils import inversion_forward_process
-from .models import load_model
 from .segments import expand_segment_grid, inversion_reverse_segments, segment_records
-from .utils import load_audio, resampler_label, set_reproducability, synthetic_clip, write_wav
 from .variants import decode_variants
 
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    p.add_argument("--device_num", type=int, default=0)
-    p.add_argument("-s", "--seed", type=int, default=None)
-    p.add_argument("--model_id", type=str, default="cvssp/audioldm2-music")
-    p.add_argument("--init_aud", type=str, default=None)
+    add_options(p, "device", "model", "clip")
     p.add_argument("--source_prompt", type=str, nargs="*", default=[""])
-    p.add_argument("--cfg_src", type=float, nargs="+", default=[3])
-    p.add_argument("--num_diffusion_steps", type=int, default=200)
-    p.add_argument("--eta", type=float, default=1.0)
-    p.add_argument("--schedule", default="sequential", choices=["sequential", "batched"])
+    add_options(p, "cfg_src", "steps", "eta", "schedule")
     p.add_argument("--target_prompt", type=str, nargs="+", required=True, help="one prompt per segment of the clip")
     p.add_argument("--target_neg_prompt", type=str, default="")
     p.add_argument("--cutoff_points", type=float, nargs="*", default=None,
@@ -41,19 +32,9 @@ def parse_args(argv=None):
     p.add_argument("--cfg_tar", type=float, nargs="+", action="append", default=None,
                    help="one guidance scale per target prompt; repeatable (default: 12 each)")
     p.add_argument("--fix_alpha", type=float, nargs="+", default=[0.1])
-    p.add_argument("--results_path", default="results")
-    p.add_argument("--allow_synthetic", action="store_true",
-                   help="run with seeded-random weights / stand-in text embeddings when no checkpoint is on disk "
-                        "(benchmarking only: the output is noise)")
-    p.add_argument("--text_t5", default="torch", choices=["torch", "native"],
-                   help="T5 text encoder: torch = transformers.T5EncoderModel, native = the encoder stack on the op tape "
-                        "(HIP kernels, one hipGraph per prompt batch shape); no effect with stand-in conditioning")
-    p.add_argument("--resampler", default="auto", choices=["auto", "sinc"],
-                   help="auto: torchaudio when installed, else scipy's polyphase stand-in; sinc: the native restatement of "
-                        "torchaudio's default resampler (HIP kernel)")
+    add_options(p, "results", "synthetic", "text_t5", "resampler")
     args = p.parse_args(argv)
-    if "stable-audio" in args.model_id:
-        p.error("Stable Audio is not supported by the segment loop (its DiT call takes one prompt)")
+    require_family(p, args.model_id, False, "Stable Audio is not supported by the segment loop (its DiT call takes one prompt)")
     P = len(args.target_prompt)
     if not 1 <= P <= 8:
         p.error(f"{P} target prompts: the segment loop takes 1 to 8")
@@ -63,9 +44,7 @@ def parse_args(argv=None):
         for v in vecs:
             if len(v) != P:
                 p.error(f"{name} {v}: {len(v)} values for {P} target prompts (one per prompt)")
-    bad = [t for v in args.tstart for t in v if not 1 <= t <= args.num_diffusion_steps]
-    if bad:
-        p.error(f"--tstart {bad} outside [1, --num_diffusion_steps={args.num_diffusion_steps}]")
+    check_tstarts(p, [t for v in args.tstart for t in v], args.num_diffusion_steps)
     cuts = args.cutoff_points
     if cuts is not None and (len(cuts) != P - 1 or any(not 0 < c < 1 for c in cuts) or cuts != sorted(cuts)):
         p.error(f"--cutoff_points {cuts}: expected {P - 1} ascending values inside (0, 1) for {P} target prompts")
@@ -76,16 +55,10 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    set_reproducability(args.seed, extreme=False)
-    device = f"cuda:{args.device_num}"
-    torch.cuda.set_device(args.device_num)
     T = args.num_diffusion_steps
-    model = load_model(args.model_id, device, T, allow_synthetic=args.allow_synthetic or None,
-                       text_t5=args.text_t5)
-    src = args.init_aud if args.init_aud else (synthetic_clip(), 16000)
-    method = None if args.resampler == "auto" else args.resampler
-    x0, sr, duration = load_audio(src, model.get_fn_STFT(), device=device, stft=True, model_sr=model.get_sr(),
-                                  resampler=method)
+    model, device = open_model(args.seed, args.device_num, args.model_id, T, allow_synthetic=args.allow_synthetic,
+                               text_t5=args.text_t5)
+    x0, sr, duration, label = load_clip(model, args.init_aud, device, args.resampler, stft=True)
     t0 = time.time()
     with torch.inference_mode():
         w0 = model.vae_encode(x0)
@@ -96,16 +69,12 @@ def main(argv=None):
         lat = inversion_reverse_segments(model, wts, zs[:Z], args.edits, eta=args.eta)
         audio = decode_variants(model, lat)
     torch.cuda.synchronize()
-    print(f"{len(args.edits)} segment edits of a {duration:.1f} s clip in {time.time() - t0:.2f} s (weights: "
-          f"{model.weights_source}; text conditioning: {model.conditioning_source}; "
-          f"resampler: {resampler_label(src, 16000, method)})")
-    os.makedirs(args.results_path, exist_ok=True)
+    print(f"{len(args.edits)} segment edits of a {duration:.1f} s clip in {time.time() - t0:.2f} s "
+          f"({provenance(model, label)})")
     records = segment_records(args.edits)
-    for rec, wav in zip(records, audio):
-        write_wav(os.path.join(args.results_path, rec["file"]), wav.reshape(1, -1).numpy(), sr=sr)
-    with open(os.path.join(args.results_path, "segments.json"), "w") as f:
-        json.dump(dict(source_prompt=args.source_prompt, cfg_src=args.cfg_src, num_diffusion_steps=T, eta=args.eta,
-                       model_id=args.model_id, segments=records), f, indent=1)
+    write_rows(args.results_path, records, audio, sr, "segments.json",
+               dict(source_prompt=args.source_prompt, cfg_src=args.cfg_src, num_diffusion_steps=T, eta=args.eta,
+                    model_id=args.model_id, segments=records))
 
 
 if __name__ == "__main__":

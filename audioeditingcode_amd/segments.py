@@ -11,7 +11,7 @@ import itertools
 
 import torch
 
-from .ddm_inversion.inversion_utils import _segment_tensors, conditioning_from_text
+from .ddm_inversion.inversion_utils import _segment_tensors, prompt_cache
 from .editing import MAX_SEGMENT_BATCH, Conditioning
 from .variants import eta_for_engine, slug
 
@@ -84,14 +84,7 @@ def inversion_reverse_segments(model, xts, zs, edits, eta=1.0):
     for k, e in enumerate(edits):
         check_edit(k, e, zs.shape[0])
     ed = model.editor(xts.shape[-2], xts.shape[-1])
-    enc, enc_neg = {}, {}
-
-    def cond(p, neg):                      # every distinct prompt is encoded once
-        box = enc_neg if neg else enc
-        if p not in box:
-            box[p] = conditioning_from_text(model, model.encode_text([p], negative=True) if neg
-                                            else model.encode_text([p]))
-        return box[p]
+    cond = prompt_cache(model)                      # every distinct prompt is encoded once
     xts_c = ed.to_nhwc(xts.unsqueeze(1))
     zs_c = ed.to_nhwc(zs.unsqueeze(1))
     rows = []

@@ -14,6 +14,7 @@ scale and solver history, and one fused SDE-DPM-Solver++ step in which every row
 """
 import torch
 
+from .ddm_inversion.inversion_utils import prompt_cache
 from .stable_audio import StableAudioEditEngine
 
 MAX_VARIANTS = StableAudioEditEngine.MAX_VARIANTS        # rows per loop; longer lists run as several calls
@@ -54,7 +55,8 @@ def inversion_reverse_clips_sa(model, inversions, edits, durations=None, first_o
     c0, Z0 = edits[order[0]][0], edits[order[0]][1].tstart
     model.setup_extra_inputs(inversions[c0][0][Z0].unsqueeze(0), init_timestep=sched.timesteps[-Z0],
                              audio_end_in_s=durations[c0])
-    enc, enc_neg, secs, ctxs = {}, {}, {}, {}
+    text = prompt_cache(model, lambda hs, _, mask: (hs, mask))
+    secs, ctxs = {}, {}
 
     def seconds(c):
         if durations[c] not in secs:
@@ -64,11 +66,7 @@ def inversion_reverse_clips_sa(model, inversions, edits, durations=None, first_o
     def ctx(p, negative, c):
         key = (p, negative, durations[c])
         if key not in ctxs:
-            box = enc_neg if negative else enc
-            if p not in box:
-                hs, _, mask = model.encode_text([p], negative=True) if negative else model.encode_text([p])
-                box[p] = (hs, mask)
-            ctxs[key] = model.assemble_context(*box[p], seconds=seconds(c)[:2])
+            ctxs[key] = model.assemble_context(*text(p, negative), seconds=seconds(c)[:2])
         return ctxs[key]
     ed = model.editor()
     n = min(int(chunk or ed.MAX_VARIANTS), ed.MAX_VARIANTS)

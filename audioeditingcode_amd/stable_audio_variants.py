@@ -11,6 +11,7 @@ DiT batch 2a for the a variants active at a step, one fused SDE-DPM-Solver++ ste
 """
 import torch
 
+from .ddm_inversion.inversion_utils import prompt_cache
 from .stable_audio import StableAudioEditEngine
 
 MAX_VARIANTS = StableAudioEditEngine.MAX_VARIANTS        # rows per loop; longer lists run as several calls
@@ -40,14 +41,7 @@ def inversion_reverse_variants_sa(model, xts, zs, variants, extra_info, duration
     # the duration embeddings and the scheduler state, once (_sa_reverse does this per edit); the history the reference
     # keeps in the scheduler is per row here, seeded inside the loop
     model.setup_extra_inputs(xts[Z].unsqueeze(0), init_timestep=sched.timesteps[-Z], audio_end_in_s=duration)
-    enc, enc_neg = {}, {}
-
-    def ctx(p, negative):
-        box = enc_neg if negative else enc
-        if p not in box:
-            hs, _, mask = model.encode_text([p], negative=True) if negative else model.encode_text([p])
-            box[p] = model.assemble_context(hs, mask)
-        return box[p]
+    ctx = prompt_cache(model, lambda hs, _, mask: model.assemble_context(hs, mask))
     ed = model.editor()
     chunk = min(int(chunk or ed.MAX_VARIANTS), ed.MAX_VARIANTS)
     xts_c, zs_c = ed.to_lc(xts), ed.to_lc(zs)

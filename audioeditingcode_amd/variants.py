@@ -12,7 +12,7 @@ import re
 
 import torch
 
-from .ddm_inversion.inversion_utils import conditioning_from_text
+from .ddm_inversion.inversion_utils import prompt_cache
 
 
 class EditVariant:
@@ -78,14 +78,7 @@ def inversion_reverse_variants(model, xts, zs, variants, etas=1.0, chunk=None):
         raise ValueError("inversion_reverse_variants: xts [T+1, C, H, W] and zs [Z, C, H, W] of ONE clip")
     ed = model.editor(xts.shape[-2], xts.shape[-1])
     chunk = min(int(chunk or ed.MAX_VARIANTS), ed.MAX_VARIANTS)
-    enc, enc_neg = {}, {}
-
-    def cond(p, neg):
-        box = enc_neg if neg else enc
-        if p not in box:
-            box[p] = conditioning_from_text(model, model.encode_text([p], negative=True) if neg
-                                            else model.encode_text([p]))
-        return box[p]
+    cond = prompt_cache(model)                      # every distinct prompt is encoded once
     xts_c = ed.to_nhwc(xts.unsqueeze(1))
     zs_c = ed.to_nhwc(zs.unsqueeze(1))
     eta = eta_for_engine(etas, zs.shape[0])

@@ -239,3 +239,43 @@ def test_three_prompts_match_the_host_driven_loop(clip):
     w_host = _reverse(clip, [6, 6, 2], **kw)
     print("P = 3: device vs host", rel(w_dev, w_host))
     assert rel(w_dev, w_host) < 2e-3, rel(w_dev, w_host)
+
+
+# ------------------------------------------------------------------------------------------------ 3. the CLI
+def test_cli_writes_one_wav_per_row_and_segments_json(tmp_path, capsys):
+    import json
+    import os
+    import wave
+
+    import numpy as np
+
+    from audioeditingcode_amd import main_run_segments
+    from audioeditingcode_amd.segments import segment_records
+    from audioeditingcode_amd.utils import synthetic_clip, write_wav
+    wav = str(tmp_path / "clip.wav")
+    write_wav(wav, synthetic_clip(seconds=1.25, seed=9), 16000)
+    out = str(tmp_path / "res")
+    argv = ["--model_id", "tiny/audioldm2", "--init_aud", wav, "--target_prompt", "jazz", "rock", "--tstart", "4", "3",
+            "--tstart", "3", "3", "--cfg_tar", "9", "6", "--fix_alpha", "0.2", "--num_diffusion_steps", "6",
+            "--source_prompt", "rain", "--results_path", out, "-s", "2"]
+    main_run_segments.main(argv)
+    txt = capsys.readouterr().out
+    assert "2 segment edits of a 1.2 s clip" in txt and "text conditioning: synthetic" in txt and "seeded-random" in txt
+    assert "resampler: none: already at the model rate" in txt
+    doc = json.load(open(os.path.join(out, "segments.json")))
+    assert list(doc) == ["source_prompt", "cfg_src", "num_diffusion_steps", "eta", "model_id", "segments"]
+    assert doc["segments"] == segment_records(main_run_segments.parse_args(argv).edits) and len(doc["segments"]) == 2
+    assert doc["num_diffusion_steps"] == 6 and doc["source_prompt"] == ["rain"] and doc["model_id"] == "tiny/audioldm2"
+    assert doc["segments"][0] == dict(index=0, target_prompt=["jazz", "rock"], target_neg_prompt="", tstart=[4, 3],
+                                      cfg_tar=[9.0, 6.0], cutoff_points=None, fix_alpha=0.2,
+                                      file="000_jazz_rock_t4-3_cfg9-6_fa0.2.wav")
+    assert [r["tstart"] for r in doc["segments"]] == [[4, 3], [3, 3]]
+    assert sorted(os.listdir(out)) == sorted([r["file"] for r in doc["segments"]] + ["segments.json"])
+    frames = []
+    for r in doc["segments"]:
+        with wave.open(os.path.join(out, r["file"])) as f:
+            assert (f.getframerate(), f.getnframes(), f.getnchannels()) == (16000, 128 * 160 + 32, 1)
+            x = np.frombuffer(f.readframes(f.getnframes()), dtype=np.int16)
+        assert np.abs(x).max() > 0
+        frames.append(x.tobytes())
+    assert len(set(frames)) == 2

@@ -219,3 +219,40 @@ def test_full_size_audioldm2_four_variants_match_their_edits():
         times[name] = time.perf_counter() - t0
     print(f"\nfull-size AudioLDM2, T={T}, tstart={tstart}, K=4: batched {times['batched'] * 1e3:.0f} ms, "
           f"4 sequential edits {times['sequential'] * 1e3:.0f} ms ({times['sequential'] / times['batched']:.2f}x)")
+
+
+# ------------------------------------------------------------------------------------------------ 4. the CLI
+def test_cli_writes_one_wav_per_variant_and_variants_json(tmp_path, capsys):
+    import json
+    import os
+    import wave
+
+    import numpy as np
+
+    from audioeditingcode_amd import main_run_variants
+    from audioeditingcode_amd.utils import synthetic_clip, write_wav
+    from audioeditingcode_amd.variants import manifest
+    wav = str(tmp_path / "clip.wav")
+    write_wav(wav, synthetic_clip(seconds=1.25, seed=9), 16000)
+    out = str(tmp_path / "res")
+    argv = ["--model_id", "tiny/audioldm2", "--init_aud", wav, "--num_diffusion_steps", "6", "--source_prompt", "rain",
+            "--target_prompt", "jazz", "rock", "--tstart", "4", "3", "--cfg_tar", "9", "--results_path", out, "-s", "3"]
+    main_run_variants.main(argv)
+    txt = capsys.readouterr().out
+    assert "4 edits of a 1.2 s clip" in txt and "text conditioning: synthetic" in txt and "seeded-random" in txt
+    assert "resampler: none: already at the model rate" in txt
+    doc = json.load(open(os.path.join(out, "variants.json")))
+    assert list(doc) == ["source_prompt", "cfg_src", "num_diffusion_steps", "eta", "model_id", "variants"]
+    assert doc["variants"] == manifest(main_run_variants.parse_args(argv).variants) and len(doc["variants"]) == 4
+    assert [(r["target_prompt"], r["tstart"]) for r in doc["variants"]] == [("jazz", 4), ("jazz", 3), ("rock", 4), ("rock", 3)]
+    assert (doc["source_prompt"], doc["cfg_src"], doc["num_diffusion_steps"], doc["eta"], doc["model_id"]) == (
+        ["rain"], [3.0], 6, 1.0, "tiny/audioldm2")
+    assert sorted(os.listdir(out)) == sorted([r["file"] for r in doc["variants"]] + ["variants.json"])
+    frames = []
+    for r in doc["variants"]:
+        with wave.open(os.path.join(out, r["file"])) as f:
+            assert (f.getframerate(), f.getnframes(), f.getnchannels()) == (16000, 128 * 160 + 32, 1)
+            x = np.frombuffer(f.readframes(f.getnframes()), dtype=np.int16)
+        assert np.abs(x).max() > 0
+        frames.append(x.tobytes())
+    assert len(set(frames)) == 4
