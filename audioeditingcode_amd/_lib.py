@@ -36,6 +36,11 @@ OP_REVERSE_STEP_SEGMENTS = 35
 OP_T5_EMBED, OP_RMSNORM, OP_T5_ATTENTION, OP_GATED_ACT = 36, 37, 38, 39
 T5_ATTN_HEAD_SIZES = (8, 16, 32, 64)    # head sizes AED_OP_T5_ATTENTION takes
 T5_ATTN_MAX_L = 512                     # its longest sequence
+# the GPT-2 language model's ops beside the GEMMs (csrc/lm.hip); tape.layernorm_rows / add_rows / gelu_new / causal_attention
+# name their records.  40 is unassigned (refused as a bad opcode)
+OP_LAYERNORM_ROWS, OP_ADD_ROWS, OP_GELU_NEW, OP_CAUSAL_ATTENTION = 41, 42, 43, 44
+LM_ATTN_HEAD_SIZES = (8, 16, 32, 64)    # head sizes AED_OP_CAUSAL_ATTENTION takes
+LM_ATTN_MAX_NK = 1024                   # its longest key/value cache
 SEG_MAX_P = 8               # prompts per row AED_OP_REVERSE_STEP_SEGMENTS takes
 PC_TAB_STRIDE = 4           # floats per slot of the ops' table: sqrt(abar_t), c0, c1, sigma_t^2 / const
 PC_MAX_EV = 8               # directions AED_OP_PC_ORTHONORMALISE takes

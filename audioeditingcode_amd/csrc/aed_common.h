@@ -64,6 +64,10 @@ int launch_t5_embed(const aed_op* op, hipStream_t s);
 int launch_rmsnorm(const aed_op* op, hipStream_t s);
 int launch_t5_attention(const aed_op* op, hipStream_t s);
 int launch_gated_act(const aed_op* op, hipStream_t s);
+int launch_layernorm_rows(const aed_op* op, hipStream_t s);
+int launch_add_rows(const aed_op* op, hipStream_t s);
+int launch_gelu_new(const aed_op* op, hipStream_t s);
+int launch_causal_attention(const aed_op* op, hipStream_t s);
 
 int aed_num_cus();
 

@@ -62,6 +62,8 @@ static launcher_t g_table[AED_OP_COUNT] = {
     launch_drift_step_variants, launch_reverse_step_rows, launch_pc_probe, launch_pc_jacobian, launch_pc_orthonormalise,
     launch_sa_step_variants, launch_reverse_step_segments,
     launch_t5_embed, launch_rmsnorm, launch_t5_attention, launch_gated_act,
+    nullptr,              // 40 is unassigned (refused as a bad opcode)
+    launch_layernorm_rows, launch_add_rows, launch_gelu_new, launch_causal_attention,
 };
 
 extern "C" {
@@ -85,7 +87,7 @@ int aed_device_info(int* cu_count, int* lds_bytes, char* arch, int arch_len) {
 
 int aed_launch(const aed_op* op, void* stream) {
     AED_REQUIRE(op != nullptr, "aed_launch: null op");
-    AED_REQUIRE(op->code >= 0 && op->code < AED_OP_COUNT, "aed_launch: bad opcode %d", op->code);
+    AED_REQUIRE(op->code >= 0 && op->code < AED_OP_COUNT && g_table[op->code] != nullptr, "aed_launch: bad opcode %d", op->code);
     return g_table[op->code](op, (hipStream_t)stream);
 }
 
@@ -93,7 +95,7 @@ int aed_tape_run(const aed_op* ops, int n, void* stream) {
     AED_REQUIRE(ops != nullptr || n == 0, "aed_tape_run: null tape");
     for (int k = 0; k < n; ++k) {
         const aed_op* op = ops + k;
-        if (op->code < 0 || op->code >= AED_OP_COUNT) {
+        if (op->code < 0 || op->code >= AED_OP_COUNT || g_table[op->code] == nullptr) {
             aed_set_error("aed_tape_run: bad opcode %d at op %d", op->code, k);
             return 2;
         }

@@ -20,6 +20,7 @@ hipcc $FLAGS -c api.hip -o obj/api.o & pids+=($!)
 hipcc $FLAGS -c image.hip -o obj/image.o & pids+=($!)
 hipcc $FLAGS -c resample.hip -o obj/resample.o & pids+=($!)
 hipcc $FLAGS -c t5.hip -o obj/t5.o & pids+=($!)
+hipcc $FLAGS -c lm.hip -o obj/lm.o & pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 hipcc --offload-arch=$ARCH -shared -fPIC obj/*.o -o ../libaed.so
 echo "built $(cd .. && pwd)/libaed.so"

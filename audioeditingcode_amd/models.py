@@ -94,7 +94,8 @@ class PipelineWrapper(torch.nn.Module):
 
     def __init__(self, model_id: str, device: torch.device, double_precision: bool = False,
                  token: Optional[str] = None, seed: int = 0, state_dicts: Optional[Dict] = None,
-                 allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None, *args, **kwargs) -> None:
+                 allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None, text_lm: Optional[str] = None,
+                 *args, **kwargs) -> None:
         super().__init__()
         self._init_common(model_id, device, double_precision, token, allow_synthetic)
         self.family = configs.get_family(model_id)
@@ -113,8 +114,11 @@ class PipelineWrapper(torch.nn.Module):
             self.weights_source = ckpt
             try:
                 from .text_encoders import TextEncoders
-                self.text_encoders = TextEncoders.from_pretrained(ckpt, self.kind, device=self.device, t5=text_t5 or "torch")
-                self.conditioning_source = f"transformers text encoders from {ckpt}" + self._t5_note(text_t5)
+                text_lm = resolve_text_lm(text_lm)
+                self.text_encoders = TextEncoders.from_pretrained(ckpt, self.kind, device=self.device, t5=text_t5 or "torch",
+                                                                  lm=text_lm)
+                self.conditioning_source = f"transformers text encoders from {ckpt}" + self._t5_note(text_t5) + \
+                    self._lm_note(text_lm)
             except (FileNotFoundError, OSError, ImportError) as e:
                 if not self.synthetic_ok:
                     raise L.AedError(f"{ckpt}: U-Net/VAE/vocoder weights were found but the text-conditioning "
@@ -169,6 +173,13 @@ class PipelineWrapper(torch.nn.Module):
             return ""
         return " (T5 encoder: native op tape)" if self.kind in ("tango", "audioldm2", "stable_audio") else \
             " (no T5 encoder in this family: --text_t5 native has no effect)"
+
+    def _lm_note(self, text_lm) -> str:
+        """What `conditioning_source` says about the language model when the native one was asked for."""
+        if text_lm != "native":
+            return ""
+        return " (GPT-2 language model: native op tape)" if self.kind == "audioldm2" else \
+            " (no language model in this family: text_lm has no effect)"
 
     def _require_device(self) -> None:
         """The product runs on HIP only.  (The CPU test suite subclasses the wrapper and overrides this hook to execute
@@ -552,7 +563,8 @@ class StableAudWrapper(PipelineWrapper):
 
     def __init__(self, model_id: str, device: torch.device, double_precision: bool = False,
                  token: Optional[str] = None, seed: int = 0, state_dicts: Optional[Dict] = None,
-                 allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None, *args, **kwargs) -> None:
+                 allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None, text_lm: Optional[str] = None,
+                 *args, **kwargs) -> None:
         torch.nn.Module.__init__(self)
         self._init_common(model_id, device, double_precision, token, allow_synthetic)
         self.family = configs.get_family(model_id)
@@ -574,7 +586,8 @@ class StableAudWrapper(PipelineWrapper):
                 from .text_encoders import TextEncoders
                 self.text_encoders = TextEncoders.from_pretrained(ckpt, "stable_audio", device=self.device,
                                                                   t5=text_t5 or "torch")
-                self.conditioning_source = f"transformers text encoder from {ckpt}" + self._t5_note(text_t5)
+                self.conditioning_source = f"transformers text encoder from {ckpt}" + self._t5_note(text_t5) + \
+                    self._lm_note(resolve_text_lm(text_lm))
             except (FileNotFoundError, OSError, ImportError) as e:
                 if not self.synthetic_ok:
                     raise L.AedError(f"{ckpt}: DiT/VAE weights were found but the text-conditioning components could "
@@ -820,20 +833,34 @@ class StableAudWrapper(PipelineWrapper):
         return UNet2DConditionOutput(sample=out), None, None
 
 
+def resolve_text_lm(text_lm: Optional[str]) -> str:
+    """"torch" or "native": the argument, or the environment variable AED_TEXT_LM when the argument is None."""
+    if text_lm is None:
+        text_lm = os.environ.get("AED_TEXT_LM") or "torch"
+    if text_lm not in ("torch", "native"):
+        raise ValueError(f"text_lm={text_lm!r}: expected 'torch' or 'native'")
+    return text_lm
+
+
 def load_model(model_id: str, device: torch.device, num_diffusion_steps: int, double_precision: bool = False,
                token: Optional[str] = None, seed: int = 0, state_dicts: Optional[Dict] = None,
-               allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None) -> PipelineWrapper:
+               allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None,
+               text_lm: Optional[str] = None) -> PipelineWrapper:
     """Substring dispatch + scheduler setup of models.py:1357-1374.  `allow_synthetic`: opt-in to seeded-random weights
     and stand-in text embeddings when no checkpoint is on disk (benchmarks / tests; see PipelineWrapper.__init__).
     `text_t5`: "torch" (default) or "native" -- which T5 encoder `TextEncoders.from_pretrained` loads for the families that
-    have one (TANGO, Stable Audio, AudioLDM2's second encoder); no effect on stand-in conditioning."""
+    have one (TANGO, Stable Audio, AudioLDM2's second encoder); no effect on stand-in conditioning.
+    `text_lm`: "torch" (default) or "native" -- whether AudioLDM2's GPT-2 prompt states come from `transformers.GPT2Model` or
+    from `lm.NativeGPT2` (one tape per prompt-batch shape); None reads the environment variable AED_TEXT_LM; no effect on
+    other families or on stand-in conditioning."""
     if text_t5 not in (None, "torch", "native"):
         raise ValueError(f"text_t5={text_t5!r}: expected 'torch' or 'native'")
+    text_lm = resolve_text_lm(text_lm)
     fam = configs.family_of(model_id)
     cls = {"tango": TangoWrapper, "audioldm2": AudioLDM2Wrapper, "audioldm": AudioLDMWrapper,
            "stable_audio": StableAudWrapper}[fam]
     ldm_stable = cls(model_id=model_id, device=device, double_precision=double_precision, token=token, seed=seed,
-                     state_dicts=state_dicts, allow_synthetic=allow_synthetic, text_t5=text_t5)
+                     state_dicts=state_dicts, allow_synthetic=allow_synthetic, text_t5=text_t5, text_lm=text_lm)
     ldm_stable.load_scheduler()
     ldm_stable.model.scheduler.set_timesteps(num_diffusion_steps, device=None)
     torch.cuda.empty_cache()

@@ -68,6 +68,29 @@ def _activation(feed_forward_proj):
     raise L.AedError(f"T5EncoderEngine: feed_forward_proj {name!r} is not supported (relu, gated-gelu / gated-gelu_new)")
 
 
+def read_checkpoint(path):
+    """(config dict, state dict on the host) of a checkpoint directory: config.json + model.safetensors | sharded safetensors |
+    pytorch_model.bin, without building a torch module."""
+    with open(os.path.join(path, "config.json")) as f:
+        cfg = json.load(f)
+    sd = {}
+    index = os.path.join(path, "model.safetensors.index.json")
+    single = os.path.join(path, "model.safetensors")
+    if os.path.exists(single) or os.path.exists(index):
+        from safetensors.torch import load_file
+        files = [single]
+        if not os.path.exists(single):
+            with open(index) as f:
+                files = sorted({os.path.join(path, v) for v in json.load(f)["weight_map"].values()})
+        for fn in files:
+            sd.update(load_file(fn))
+    elif os.path.exists(os.path.join(path, "pytorch_model.bin")):
+        sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
+    else:
+        raise FileNotFoundError(f"{path}: no model.safetensors, model.safetensors.index.json or pytorch_model.bin")
+    return {k: v for k, v in cfg.items() if not k.startswith("_")}, sd
+
+
 class T5EncoderEngine:
     """A Hugging Face T5 encoder (state dict + config) on the op tape.  `encode(input_ids, attention_mask)` -> the last hidden
     state [B, L, d_model], fp32 on the device; padded positions are computed too, as transformers does."""
@@ -271,24 +294,7 @@ class NativeT5Encoder:
     def from_pretrained(cls, path, device):
         """From a checkpoint directory (config.json + model.safetensors | sharded safetensors | pytorch_model.bin) without
         building a torch module."""
-        with open(os.path.join(path, "config.json")) as f:
-            cfg = json.load(f)
-        sd = {}
-        index = os.path.join(path, "model.safetensors.index.json")
-        single = os.path.join(path, "model.safetensors")
-        if os.path.exists(single) or os.path.exists(index):
-            from safetensors.torch import load_file
-            files = [single]
-            if not os.path.exists(single):
-                with open(index) as f:
-                    files = sorted({os.path.join(path, v) for v in json.load(f)["weight_map"].values()})
-            for fn in files:
-                sd.update(load_file(fn))
-        elif os.path.exists(os.path.join(path, "pytorch_model.bin")):
-            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
-        else:
-            raise FileNotFoundError(f"{path}: no model.safetensors, model.safetensors.index.json or pytorch_model.bin")
-        cfg = {k: v for k, v in cfg.items() if not k.startswith("_")}
+        cfg, sd = read_checkpoint(path)
         cfg.setdefault("model_type", "t5")
         return cls(T5EncoderEngine(cfg, sd, device), SimpleNamespace(**cfg))
 

@@ -647,6 +647,46 @@ class Tape:
                   nbytes=12 * rows * F)
         return out
 
+    # ------------------------------------------------------------------ GPT-2 language model ops (csrc/lm.hip)
+    def layernorm_rows(self, x, g, b, out, *, rows, width, eps, ldx=None, ldy=None, name="layernorm_rows"):
+        """LayerNorm with bias over rows of x[rows, ldx]: out = (x - mean) / sqrt(var + eps) * g + b (AED_OP_LAYERNORM_ROWS);
+        a row stride above the width normalises one row per batch item of a [B, S, width] buffer."""
+        ldx = x.stride(-2) if ldx is None else ldx
+        ldy = out.stride(-2) if ldy is None else ldy
+        self._add(L.OP_LAYERNORM_ROWS, [rows & 0xFFFFFFFF, rows >> 32, width, ldx, ldy], [eps], [x, g, b, out], name=name,
+                  nbytes=8 * rows * width)
+        return out
+
+    def add_rows(self, x, table, out, *, B, R, width, r0=0, ldx=None, ldo=None, bsx=None, bso=None, name="add_rows"):
+        """out[b, r, :width] = x[b, r, :width] + table[r0 + r, :width] for r < R (AED_OP_ADD_ROWS); x and out are
+        [B, >= R, ld] views (or take ldx / ldo and the batch strides bsx / bso explicitly), table [rows, ldt]."""
+        ldx = x.stride(-2) if ldx is None else ldx
+        ldo = out.stride(-2) if ldo is None else ldo
+        bsx = x.stride(0) if bsx is None else bsx
+        bso = out.stride(0) if bso is None else bso
+        self._add(L.OP_ADD_ROWS, [B, R, width, ldx, ldo, r0, table.stride(-2), table.shape[-2], bsx, bso], [], [x, table, out],
+                  name=name, nbytes=12 * B * R * width)
+        return out
+
+    def gelu_new(self, x, out, *, rows, width, ld_in=None, ld_out=None, name="gelu_new"):
+        """out[r, c] = gelu_new(x[r, c]) for c < width (AED_OP_GELU_NEW); out may be x."""
+        ld_in = x.stride(-2) if ld_in is None else ld_in
+        ld_out = out.stride(-2) if ld_out is None else ld_out
+        self._add(L.OP_GELU_NEW, [rows & 0xFFFFFFFF, rows >> 32, width, ld_in, ld_out], [], [x, out], name=name,
+                  nbytes=8 * rows * width)
+        return out
+
+    def causal_attention(self, q, k, v, keymask, out, *, B, H, Nq, q0, D, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, bsm=0,
+                         name="causal_attn"):
+        """Nq query rows at positions q0 .. q0+Nq-1 against the Nk = q0 + Nq live rows of a key/value cache, keys j <= position,
+        scores scaled by 1/sqrt(D) (AED_OP_CAUSAL_ATTENTION): q, k, v, out are views whose row r of batch item b sits at
+        b*bs + r*ld, keymask a device int32 view with key j of batch item b at b*bsm + j, or None."""
+        Nk = q0 + Nq
+        self._add(L.OP_CAUSAL_ATTENTION, [B, H, Nq, q0, D, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, bsm], [],
+                  [q, k, v, keymask, out], name=name, flops=4 * B * H * D * (Nq * q0 + Nq * (Nq + 1) // 2),
+                  nbytes=4 * B * H * D * (2 * Nq + 2 * Nk))
+        return out
+
     def reflect_pad(self, src, dst, *, B, N, pad, ldd, name="reflect_pad"):
         self._add(L.OP_REFLECT_PAD, [B, N, pad, ldd], [], [src, dst], name=name, nbytes=8 * B * N)
 

@@ -130,13 +130,16 @@ class TextEncoders:
 
     # ------------------------------------------------------------------ loading
     @classmethod
-    def from_pretrained(cls, root: str, kind: str, device="cpu", t5="torch"):
+    def from_pretrained(cls, root: str, kind: str, device="cpu", t5="torch", lm="torch"):
         """Load from a diffusers-style snapshot directory (tokenizer/, text_encoder/, tokenizer_2/, text_encoder_2/,
         language_model/, projection_model/).  Raises if a required sub-directory is missing.  t5="native" puts a
-        `t5.NativeT5Encoder` (the encoder stack on the op tape) where the T5 module goes; everything else stays."""
+        `t5.NativeT5Encoder` (the encoder stack on the op tape) where the T5 module goes, lm="native" a `lm.NativeGPT2` (the
+        whole continuous generation as one tape) where AudioLDM2's GPT-2 goes; everything else stays."""
         from transformers import AutoTokenizer
         if t5 not in ("torch", "native"):
             raise ValueError(f"t5={t5!r}: expected 'torch' or 'native'")
+        if lm not in ("torch", "native"):
+            raise ValueError(f"lm={lm!r}: expected 'torch' or 'native'")
 
         def load_t5(path):
             if t5 == "native":
@@ -183,7 +186,11 @@ class TextEncoders:
         else:
             proj.load_state_dict(torch.load(os.path.join(proj_dir, "diffusion_pytorch_model.bin"), map_location="cpu",
                                             weights_only=True))
-        lm = GPT2Model.from_pretrained(need("language_model")).to(device)
+        if lm == "native":
+            from .lm import NativeGPT2
+            lm = NativeGPT2.from_pretrained(need("language_model"), device)
+        else:
+            lm = GPT2Model.from_pretrained(need("language_model")).to(device)
         return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")),
                    ClapModel.from_pretrained(need("text_encoder")).to(device),
                    AutoTokenizer.from_pretrained(need("tokenizer_2")),
@@ -210,8 +217,12 @@ class TextEncoders:
     @torch.no_grad()
     def generate_language_model(self, inputs_embeds, attention_mask=None, max_new_tokens=None):
         """AudioLDM2Pipeline.generate_language_model: continuous autoregression -- the last hidden state of each pass
-        is appended to the input embeddings (mask extended by ones); returns the `max_new_tokens` generated states."""
+        is appended to the input embeddings (mask extended by ones); returns the `max_new_tokens` generated states.
+        A language model that has `generate_states` (lm.NativeGPT2) runs the whole loop itself."""
         n = max_new_tokens or self.max_new_tokens
+        generate_states = getattr(self.language_model, "generate_states", None)
+        if generate_states is not None:
+            return generate_states(inputs_embeds, attention_mask, n)
         for _ in range(n):
             out = self.language_model(inputs_embeds=inputs_embeds, attention_mask=attention_mask, return_dict=True)
             inputs_embeds = torch.cat([inputs_embeds, out.last_hidden_state[:, -1:, :]], dim=1)

@@ -178,6 +178,44 @@ enum aed_opcode {
                                  slots: p0=in [rows][ld_in] p1=out [rows][ld_out]; i0,i1=rows lo/hi i2=F i3=ld_in i4=ld_out.
                                  Refused: null pointers, rows < 1, an F, ld_in or ld_out that is no multiple of 4, ld_in < 2F,
                                  ld_out < F, unaligned pointers                                                               */
+    /* 40 is unassigned: a record with code 40 is refused as a bad opcode, as it was before 41-44 existed.                   */
+    /* 41-44: what the GPT-2 language model of AudioLDM2 needs beside the GEMMs (csrc/lm.hip; audioeditingcode_amd/lm.py builds
+       the tape: one prefill pass plus single-row decode passes over a key/value cache).  fp32, no atomics, every sum in a
+       fixed order: a launch is bit-repeatable.  Buffers, row strides and batch strides are multiples of 4 floats and 16-byte
+       aligned (whole rows move as 16-byte accesses).                                                                       */
+    AED_OP_LAYERNORM_ROWS = 41, /* y = (x - mean) * (1 / sqrt(var + eps)) * g + b per row, one wave per row; the variance is
+                                 the mean of the squared deviations from the mean (never E[x^2] - mean^2), a constant row gives
+                                 exactly b.  A row stride above the width normalises one row per batch item of a [B, S, d]
+                                 buffer.
+                                 slots: p0=x [rows][ldx] p1=g [width] p2=b [width] p3=y [rows][ldy] (may be x); i0,i1=rows lo/hi
+                                 i2=width i3=ldx i4=ldy; f0=eps.  Refused: null pointers, rows < 1, a width that is no multiple
+                                 of 32 in [32, 4096], strides below the width or no multiple of 4, eps <= 0, unaligned pointers*/
+    AED_OP_ADD_ROWS = 42,     /* out[b][r][:] = x[b][r][:] + table[r0 + r][:] for r < R (learned position embeddings).
+                                 slots: p0=x (row r of batch item b at b*bsx + r*ldx) p1=table [table_rows][ldt] p2=out
+                                 (b*bso + r*ldo; may be x); i0=B i1=R i2=width i3=ldx i4=ldo i5=r0 i6=ldt i7=table_rows i8=bsx
+                                 i9=bso.  Refused: null pointers, B or R < 1, a width or stride that is no multiple of 4, row
+                                 strides below the width, r0 < 0 or r0 + R > table_rows, negative batch strides, unaligned
+                                 pointers                                                                                     */
+    AED_OP_GELU_NEW = 43,     /* out = gelu_new(in) elementwise over the rows of a strided buffer, gelu_new(x) = 0.5 x (1 +
+                                 tanh(sqrt(2/pi) (x + 0.044715 x^3))); may run in place.  (The GEMM epilogues have no such
+                                 activation.)
+                                 slots: p0=in [rows][ld_in] p1=out [rows][ld_out]; i0,i1=rows lo/hi i2=width i3=ld_in i4=ld_out.
+                                 Refused: null pointers, rows < 1, a width or stride that is no multiple of 4, strides below
+                                 the width, unaligned pointers                                                                */
+    AED_OP_CAUSAL_ATTENTION = 44, /* per (batch item b, head h): Nq query rows at sequence positions q0 .. q0+Nq-1 attend the keys
+                                 j <= position of a cache whose rows [0, Nk = q0 + Nq) are live: out = softmax(q.k^T / sqrt(D)
+                                 + keymask[b][j]) . v.  Nq = Nk is a prefill pass, Nq = 1 a decode step.  q, k, v and out each
+                                 have a row stride and a batch stride of their own (the cache may be allocated for more rows
+                                 than are live); head h sits in columns [h*D, (h+1)*D) of each pointer.  A masked key (keymask 0)
+                                 has weight exactly 0; cache rows at or beyond Nk are never loaded, so stale or NaN rows there
+                                 cannot reach the output; a query row without an attended key gives zeros.  Keys run in tiles
+                                 of 64 with a running maximum and sum.
+                                 slots: p0=q p1=k p2=v p3=keymask int32, key j of batch item b at b*bsm + j (null: no key
+                                 masked) p4=out; i0=B i1=H i2=Nq i3=q0 i4=D i5=ldq i6=ldk i7=ldv i8=ldo i9=bsq i10=bsk i11=bsv
+                                 i12=bso i13=bsm.  Refused: null pointers (p3 excepted), D outside {8, 16, 32, 64}, Nq < 1,
+                                 q0 < 0, q0 + Nq > 1024, B or H < 1, a row stride below H*D or no multiple of 4, batch strides
+                                 that are negative or no multiple of 4, an out batch stride below one batch item, bsm < Nk,
+                                 unaligned q / k / v, more than 2^31 workgroups                                               */
     AED_OP_COUNT
 };
 
