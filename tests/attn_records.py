@@ -1,7 +1,9 @@
 """Small attention records launched through the C ABI and checked against fp64: the machinery of
-test_gpu_zz_attn_records.py (the GPU side) and test_attn_records_cpu.py (the conditions that keep that suite honest).  Only the
-fp32 kernels of csrc/attention.hip are meant: attention_kernel<D> ("single"), attention_t_kernel<D, 4> ("t_ks4") and
-attention_t_kernel<D, 1> ("t_ks1").
+test_gpu_zz_attn_records.py and test_gpu_zz_attn_x6_records.py (the GPU side) and test_attn_records_cpu.py (the conditions that
+keep those suites honest).  The first part is about the fp32 kernels of csrc/attention.hip: attention_kernel<D> ("single"),
+attention_t_kernel<D, 4> ("t_ks4") and attention_t_kernel<D, 1> ("t_ks1"); the last part (from branch_x6 on) adds what the
+split-bf16 kernel of csrc/attention_x6.hip needs on top: its cases, the `flat` statistic, an L2 criterion and a CPU model of its
+arithmetic.
 
 `AttnRec` holds one hand-written AED_OP_ATTENTION record (slots as the comment above launch_attention: p0..p4 = q k v bias out,
 i0..i14 = B H Nq Nk D ldq ldk ldv ldo ld_bias bsq bsk bsv bso variant, f0 = scale) and launches it with aed_launch directly, so
@@ -41,6 +43,7 @@ GUARD_ROWS = 2
 LAYOUTS = ("qkv", "q_kv", "plain", "padded")
 BIAS_STATS = ("masked", "masked_head", "masked_1e30")
 STATS = ("base", "hot", "rising", "falling", "common", "late_peak", "first_peak", "voffset") + BIAS_STATS
+X6_STATS = STATS + ("flat",)     # the split-bf16 kernel's suite only (x6_case_stats); the fp32 suite runs STATS
 BRANCHES = ("single", "t_ks4", "t_ks1")
 HEAD_DIMS = (16, 32, 48, 64, 80)
 
@@ -187,8 +190,10 @@ def make_operands(stat, B, H, Nq, Nk, D, has_bias, seed=1):
       late_peak   the last key (in the ragged tile of a ragged case) holds more than 0.99 of every row's mass
       first_peak  key 0 does
       voffset     v = randn + 100: the output is about 100, an error in the row sum l shows absolutely
-      masked / masked_head / masked_1e30   base operands under make_bias's bias"""
-    if stat not in STATS:
+      masked / masked_head / masked_1e30   base operands under make_bias's bias
+      flat        (X6_STATS only) q x 0.05: near-uniform probabilities with full mantissas -- every key's value carries the
+                  same weight, so what the second contraction loses of p or v shows"""
+    if stat not in X6_STATS:
         raise ValueError(stat)
     assert has_bias or stat not in BIAS_STATS
     g = torch.Generator().manual_seed(seed)
@@ -198,6 +203,8 @@ def make_operands(stat, B, H, Nq, Nk, D, has_bias, seed=1):
     v = torch.randn(B, Nk, C, generator=g)
     if stat == "hot":
         q, k = q * 3, k * 3
+    elif stat == "flat":
+        q = q * 0.05
     elif stat in ("rising", "falling"):
         q = q.abs() + 0.1
         w = torch.randn(C, generator=g).abs() + 0.1
@@ -456,3 +463,150 @@ def bitwise_equal_any(t, value):
 
 def bitwise_equal(a, b):
     return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The split-bf16 kernel of csrc/attention_x6.hip (test_gpu_zz_attn_x6_records.py; its conditions in test_attn_records_cpu.py).
+# attention_x6_kernel ("x6": variant 3, or flag bit 2 in the throughput regime) and attention_x6_ref_kernel ("x6_ref":
+# variant 4, the bit reference), D = 32 / 48 / 64.  Same arena, same layouts, same max-abs bound; on top of it an L2 criterion
+#     |y - ref64|_2 <= 3 |ref32 - ref64|_2            (X6_L2_STATS; no floor)
+# because the max-abs bound alone does not see a second contraction that lost a piece (test_attn_records_cpu.py shows both).
+X6_HEAD_DIMS = (32, 48, 64)
+X6_L2_STATS = ("base", "hot", "rising", "falling", "common", "voffset", "masked", "flat")
+#   not there: late_peak / first_peak (ref32 is exact to 1e-11: one key holds the mass) and masked_head / masked_1e30 (there can
+#   be one key left); those four rely on the max-abs bound with its floor
+X6_L2_MIN = 5e-8            # the L2 criterion applies where ref32's own relative L2 error is at least this: never degenerate
+
+
+def branch_x6(B, H, Nq, Nk, D, variant, flags, cus, aligned=True):
+    """Python mirror of launch_attention with flags and variants 3 / 4: "x6" | "x6_ref" | "refused" (a forced variant the
+    split-bf16 kernel does not take: AED_REQUIRE fails before any launch) | branch(...)'s three.  aligned: q and k 16-byte
+    aligned (launch_attention_x6's float4 fragment loads)."""
+    takes = D in X6_HEAD_DIMS and aligned
+    if variant in (3, 4):
+        return ("x6" if variant == 3 else "x6_ref") if takes else "refused"
+    if Nk > 64 and variant != 1:
+        ks4 = _cdiv(Nq, 128) * H * B < 2 * cus
+        if flags & 4 and not ks4 and takes:
+            return "x6"
+        return "t_ks4" if ks4 else "t_ks1"
+    return "single"
+
+
+# id -> (D, layout, bias, H, B, Nq, Nk, variant, AttnRec keywords), as the tables above.  X1 .. X10 force the kernel (variant
+# 3) at a small batch; XF1 .. XF3 carry flag bit 2 at the throughput batch, as the tapes built under arith_mode("bf16x6") do.
+# With nfull = Nk // 32 the kernel's mask-free loop runs tiles [0, nmain), nmain = nfull & ~1, and the tail, if
+# nmain < cdiv(Nk, 32), runs tiles nmain and nmain + 1 with the mask test (x6_tail).
+X6 = {
+    "X1": (32, "qkv", False, 2, 2, 256, 256, 3, {}),       # shipped class; even tile count: the mask-free loop alone, no tail
+    "X2": (48, "qkv", False, 2, 1, 100, 100, 3, {}),       # shipped; a full tile inside the tail and a 4-key ragged tile; D = 48
+    #                                                        (zero-padded V^T rows, the loader slot that is K in waves 0 and 1
+    #                                                        and V in waves 2 and 3); a partial wave; 2 workgroups (the XCD
+    #                                                        remap's remainder branch)
+    "X3": (64, "qkv", False, 3, 1, 129, 129, 3, {}),       # shipped (Stable Audio self); one-key tail and dead tile; a workgroup
+    #                                                        with one query
+    "X4": (64, "q_kv", False, 2, 2, 33, 130, 3, {}),       # shipped (Stable Audio cross); ld = 2C
+    "X5": (48, "q_kv", True, 2, 2, 40, 70, 3, {}),         # bias of batch item 1; 6-key tail and dead tile
+    "X6": (32, "padded", True, 3, 2, 130, 97, 3, {}),      # ldk != ldv, padded ld_bias, ldo > C; a full tile then a one-key
+    #                                                        tile in the tail
+    "X7": (64, "padded", False, 2, 2, 70, 96, 3, {}),      # odd count, Nk % 32 == 0: only the dead tile is masked
+    "X8": (48, "plain", True, 2, 3, 33, 33, 3, {}),        # forced short keys: nmain = 0
+    "X9": (32, "q_kv", False, 2, 2, 70, 5, 3, {}),         # Nk < 32: tile 0 ragged, tile 1 dead
+    "X10": (64, "plain", True, 2, 2, 128, 64, 3, {}),      # bias read with no mask code at all
+    "XF1": (32, "qkv", False, 4, None, 96, 96, 0, dict(flags=4)),
+    "XF2": (48, "qkv", False, 4, None, 70, 70, 0, dict(flags=4)),
+    "XF3": (64, "q_kv", False, 4, None, 33, 130, 0, dict(flags=4)),
+}
+X6_FORCED = tuple(c for c in X6 if X6[c][7] == 3)
+X6_FLAGGED = tuple(c for c in X6 if X6[c][7] == 0)
+
+
+def x6_case_stats(case):
+    """The statistics of X6_STATS that apply to a case."""
+    return tuple(s for s in X6_STATS if case[2] or s not in BIAS_STATS)
+
+
+def x6_tail(Nk):
+    """What attention_x6_kernel's tail runs for Nk keys: () (no tail) or the two tiles' kinds, "full" | "ragged" | "dead"."""
+    nmain, ntiles = (Nk // 32) & ~1, _cdiv(Nk, 32)
+    kind = lambda t: "dead" if t >= ntiles else "full" if 32 * t + 32 <= Nk else "ragged"       # noqa: E731
+    return () if nmain >= ntiles else (kind(nmain), kind(nmain + 1))
+
+
+# the six piece products with i + j <= 2 in ax6_mfma6's order, smallest first: (piece of the A operand, piece of the B operand);
+# A is K (scores) or V (output), B is Q or P
+SIX = ((0, 2), (2, 0), (1, 1), (0, 1), (1, 0), (0, 0))
+THREE = ((0, 1), (1, 0), (0, 0))
+NO_MID_MID = tuple(t for t in SIX if t != (1, 1))
+
+
+def bf16_pieces(x, n=3):
+    """x (float32) -> [hi, mid, lo][:n] as float32 tensors holding bf16 values, each the round-to-nearest bf16 of what the
+    pieces before it left; hi + mid + lo == x exactly."""
+    out, r = [], x
+    for _ in range(n):
+        piece = r.bfloat16().float()
+        out.append(piece)
+        r = r - piece
+    return out
+
+
+def x6_model(q, k, v, bias, H, D, *, score_terms=SIX, pv_terms=SIX, pieces=(3, 3, 3, 3)):
+    """The ARITHMETIC of the split-bf16 kernel in torch float32 on the CPU -- never the GPU yardstick; it shows that the bounds
+    are attainable by that arithmetic and that they see a wrong one.  q pre-scaled, then q, k, v and the probabilities split
+    into pieces = (q, k, p, v) round-to-nearest bf16 pieces; per 32-key tile the scores accumulate, per 16-wide d block, the
+    `score_terms` piece products in that order (each an exact bf16 x bf16 product summed in float32), the tile joins an online
+    softmax (running maximum, each lane half's share of the row sum, rescale by exp(m_old - m_new)), and the output
+    accumulates, per 16-key block, the `pv_terms` products; 1 / l multiplies at the end.  A term that names a piece the operand
+    does not have is dropped.  Shares no code with the kernel: no staging order, no lanes, torch's exp and matmul."""
+    B, Nq, Nk = q.shape[0], q.shape[1], k.shape[1]
+    nq, nk, npp, nv = pieces
+    heads = lambda t: t.reshape(B, -1, H, D).transpose(1, 2).contiguous()                       # noqa: E731
+    pad = _cdiv(Nk, 32) * 32 - Nk                               # keys past Nk read as 0 and leave through the mask
+    qh = heads(q * torch.tensor(D ** -0.5, dtype=torch.float32))
+    kh, vh = (torch.nn.functional.pad(heads(t), (0, 0, 0, pad)) for t in (k, v))
+    qp, kp, vp = bf16_pieces(qh, nq), bf16_pieces(kh, nk), bf16_pieces(vh, nv)
+    m = torch.full((B, H, Nq, 1), float("-inf"))
+    l2 = torch.zeros(B, H, Nq, 2)                               # the two lane halves' shares of the row sum
+    o = torch.zeros(B, H, Nq, D)
+    for k0 in range(0, Nk, 32):
+        s = torch.zeros(B, H, Nq, 32)
+        for d0 in range(0, D, 16):
+            for a, b in score_terms:
+                if a < nk and b < nq:
+                    s = s + qp[b][..., d0:d0 + 16] @ kp[a][:, :, k0:k0 + 32, d0:d0 + 16].transpose(-1, -2)
+        if bias is not None:
+            s = s + torch.nn.functional.pad(bias, (0, pad))[:, None, None, k0:k0 + 32]
+        if k0 + 32 > Nk:
+            s[..., Nk - k0:] = float("-inf")
+        mn = torch.maximum(m, s.amax(-1, keepdim=True))
+        alpha = torch.exp(m - mn)
+        m = mn
+        p = torch.exp(s - mn)
+        # a lane half fh holds keys k0 + (r & 3) + 8 (r >> 2) + 4 fh: the keys with bit 2 equal to fh
+        l2 = l2 * alpha + p.reshape(B, H, Nq, 4, 2, 4).sum((3, 5))
+        o = o * alpha
+        pp = bf16_pieces(p, npp)
+        for j0 in range(0, 32, 16):
+            for a, b in pv_terms:
+                if a < nv and b < npp:
+                    o = o + pp[b][..., j0:j0 + 16] @ vp[a][:, :, k0 + j0:k0 + j0 + 16]
+    return _merge_heads(o * (1.0 / l2.sum(-1, keepdim=True)))
+
+
+X6_MUTANTS = {  # name: (the statistic under which the L2 criterion must see it, x6_model keywords)
+    "three_term_scores": ("hot", dict(score_terms=THREE)),
+    "no_mid_mid_scores": ("hot", dict(score_terms=NO_MID_MID)),
+    "k_two_pieces": ("hot", dict(pieces=(3, 2, 3, 3))),
+    "q_two_pieces": ("hot", dict(pieces=(2, 3, 3, 3))),
+    "three_term_pv": ("flat", dict(pv_terms=THREE)),
+    "no_mid_mid_pv": ("flat", dict(pv_terms=NO_MID_MID)),
+    "p_two_pieces": ("flat", dict(pieces=(3, 3, 2, 3))),
+    "v_two_pieces": ("flat", dict(pieces=(3, 3, 3, 2))),
+}
+
+
+def l2_ratio(y, r64, l2_32):
+    """|y - ref64|_2 / |ref32 - ref64|_2 from bound3's figures (l2_32 = ref32's relative L2 error); nan where ref32 is exact
+    (one key left: the L2 criterion does not apply there)."""
+    return float((y.double() - r64).norm() / r64.norm()) / l2_32 if l2_32 > 0 else float("nan")
