@@ -7,24 +7,11 @@
 // All fp32, wave64, no atomics; every sum runs in a fixed order (lane-strided partial sums, then an xor butterfly over the
 // wave, whose two operands commute), so a launch is bit-repeatable.  The language model sees a few dozen tokens: these
 // kernels are latency-bound, and the contractions of the attention (D <= 64, Nk <= 1024) stay on the vector ALU.
-#include "aed_common.h"
+// The attention is the tile body of text_attn_tile.h under LmPolicy (t5.hip runs the same body with a position bias); the
+// wave butterflies, gelu_new and the launchers' small helpers are those of rows_common.h, shared with t5.hip.
+#include "text_attn_tile.h"
 
-#define LM_WAVES 4                          // waves per workgroup of the row kernels and the attention (256 threads)
-
-__device__ __forceinline__ float lm_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float lm_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-static inline bool lm_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static inline long long lm_rows64(const aed_op* op) {
-    return (long long)((uint64_t)(uint32_t)op->i[0] | ((uint64_t)(uint32_t)op->i[1] << 32));
-}
+#define LM_WAVES 4                          // waves per workgroup of the one-wave-per-row kernels (256 threads)
 
 // ------------------------------------------------------------------------------------ LayerNorm with bias
 // One wave per row, the row held in registers (<= 16 float4 a lane).  The mean is taken in two steps: mean1 = pivot +
@@ -55,7 +42,7 @@ __global__ __launch_bounds__(64 * LM_WAVES) void lm_layernorm_rows_kernel(const 
         xv[t] = v < n4 ? xr[v] : make_float4(pivot, pivot, pivot, pivot);
         s += ((xv[t].x - pivot) + (xv[t].y - pivot)) + ((xv[t].z - pivot) + (xv[t].w - pivot));
     }
-    const float mean1 = pivot + lm_wave_sum(s) / (float)width;
+    const float mean1 = pivot + aed_wave_sum(s) / (float)width;
     float c = 0.f;
 #pragma unroll
     for (int t = 0; t < LM_LN_MAXV; ++t) {
@@ -65,7 +52,7 @@ __global__ __launch_bounds__(64 * LM_WAVES) void lm_layernorm_rows_kernel(const 
             c += (xv[t].x + xv[t].y) + (xv[t].z + xv[t].w);
         }
     }
-    c = lm_wave_sum(c) / (float)width;
+    c = aed_wave_sum(c) / (float)width;
     float ss = 0.f;
 #pragma unroll
     for (int t = 0; t < LM_LN_MAXV; ++t) {
@@ -75,7 +62,7 @@ __global__ __launch_bounds__(64 * LM_WAVES) void lm_layernorm_rows_kernel(const 
             ss += (xv[t].x * xv[t].x + xv[t].y * xv[t].y) + (xv[t].z * xv[t].z + xv[t].w * xv[t].w);
         }
     }
-    const float r = 1.0f / sqrtf(lm_wave_sum(ss) / (float)width + eps);
+    const float r = 1.0f / sqrtf(aed_wave_sum(ss) / (float)width + eps);
 #pragma unroll
     for (int t = 0; t < LM_LN_MAXV; ++t) {
         if (64 * t >= n4) break;
@@ -95,7 +82,7 @@ int launch_layernorm_rows(const aed_op* op, hipStream_t s) {
     const float* g = (const float*)op->p[1];
     const float* b = (const float*)op->p[2];
     float* y = (float*)op->p[3];
-    const long long rows = lm_rows64(op);
+    const long long rows = aed_rows64(op);
     const int width = op->i[2], ldx = op->i[3], ldy = op->i[4];
     const float eps = op->f[0];
     AED_REQUIRE(x && g && b && y, "layernorm_rows: null pointer (x %p, g %p, b %p, y %p)", (const void*)x, (const void*)g,
@@ -106,7 +93,7 @@ int launch_layernorm_rows(const aed_op* op, hipStream_t s) {
     AED_REQUIRE(ldx >= width && ldx % 4 == 0 && ldy >= width && ldy % 4 == 0,
                 "layernorm_rows: row strides (ldx %d, ldy %d) must be multiples of 4 and at least the width %d", ldx, ldy, width);
     AED_REQUIRE(eps > 0.f, "layernorm_rows: eps %g must be positive (a constant row has variance 0)", (double)eps);
-    AED_REQUIRE(lm_aligned16(x) && lm_aligned16(g) && lm_aligned16(b) && lm_aligned16(y),
+    AED_REQUIRE(aed_aligned16(x) && aed_aligned16(g) && aed_aligned16(b) && aed_aligned16(y),
                 "layernorm_rows: x, g, b and y must be 16-byte aligned");
     hipLaunchKernelGGL(lm_layernorm_rows_kernel, dim3((unsigned)((rows + LM_WAVES - 1) / LM_WAVES)), dim3(64 * LM_WAVES), 0, s, x,
                        g, b, y, rows, width, (long long)ldx, (long long)ldy, eps);
@@ -151,7 +138,7 @@ int launch_add_rows(const aed_op* op, hipStream_t s) {
                 r0 + R, trows);
     AED_REQUIRE(bsx >= 0 && bso >= 0 && bsx % 4 == 0 && bso % 4 == 0 && (B == 1 || bso >= width),
                 "add_rows: batch strides (bsx %d, bso %d) must be non-negative multiples of 4, bso at least the width", bsx, bso);
-    AED_REQUIRE(lm_aligned16(x) && lm_aligned16(table) && lm_aligned16(out), "add_rows: x, table and out must be 16-byte aligned");
+    AED_REQUIRE(aed_aligned16(x) && aed_aligned16(table) && aed_aligned16(out), "add_rows: x, table and out must be 16-byte aligned");
     const long long waves = (long long)B * R;
     hipLaunchKernelGGL(lm_add_rows_kernel, dim3((unsigned)((waves + LM_WAVES - 1) / LM_WAVES)), dim3(64 * LM_WAVES), 0, s, x, table,
                        out, B, R, width, ldx, ldo, r0, ldt, (long long)bsx, (long long)bso);
@@ -160,11 +147,6 @@ int launch_add_rows(const aed_op* op, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------ gelu_new
-// (the expression of t5.hip's t5_gelu_new)
-__device__ __forceinline__ float lm_gelu_new(float x) {
-    return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
-}
-
 __global__ __launch_bounds__(256) void lm_gelu_new_kernel(const float* in, float* out, long long rows, int width, int ld_in,
                                                           int ld_out) {
     const int w4 = width / 4;
@@ -174,7 +156,7 @@ __global__ __launch_bounds__(256) void lm_gelu_new_kernel(const float* in, float
         const int c = (int)(e - r * w4);
         const float4 a = ((const float4*)(in + (size_t)r * (size_t)ld_in))[c];
         ((float4*)(out + (size_t)r * (size_t)ld_out))[c] =
-            make_float4(lm_gelu_new(a.x), lm_gelu_new(a.y), lm_gelu_new(a.z), lm_gelu_new(a.w));
+            make_float4(aed_gelu_new(a.x), aed_gelu_new(a.y), aed_gelu_new(a.z), aed_gelu_new(a.w));
     }
 }
 
@@ -183,14 +165,14 @@ __global__ __launch_bounds__(256) void lm_gelu_new_kernel(const float* in, float
 int launch_gelu_new(const aed_op* op, hipStream_t s) {
     const float* in = (const float*)op->p[0];
     float* out = (float*)op->p[1];
-    const long long rows = lm_rows64(op);
+    const long long rows = aed_rows64(op);
     const int width = op->i[2], ld_in = op->i[3], ld_out = op->i[4];
     AED_REQUIRE(in && out, "gelu_new: null pointer (in %p, out %p)", (const void*)in, (void*)out);
     AED_REQUIRE(rows > 0 && rows <= (1LL << 32), "gelu_new: rows %lld outside [1, 2^32]", rows);
     AED_REQUIRE(width > 0 && width % 4 == 0 && width <= (1 << 28), "gelu_new: width %d must be a positive multiple of 4", width);
     AED_REQUIRE(ld_in >= width && ld_in % 4 == 0 && ld_out >= width && ld_out % 4 == 0,
                 "gelu_new: row strides (ld_in %d, ld_out %d) must be multiples of 4 and at least the width %d", ld_in, ld_out, width);
-    AED_REQUIRE(lm_aligned16(in) && lm_aligned16(out), "gelu_new: in and out must be 16-byte aligned");
+    AED_REQUIRE(aed_aligned16(in) && aed_aligned16(out), "gelu_new: in and out must be 16-byte aligned");
     const long long blocks = (rows * (width / 4) + 255) / 256;
     const long long cap = 256LL * 8;
     hipLaunchKernelGGL(lm_gelu_new_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, s, in, out, rows, width,
@@ -200,9 +182,6 @@ int launch_gelu_new(const aed_op* op, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------ causal attention over a key/value cache
-#define LMA_QT 16                           // query rows per workgroup (LMA_QT / LM_WAVES per wave)
-#define LMA_KT 64                           // keys per tile: one per lane
-#define LMA_RPW (LMA_QT / LM_WAVES)
 #define LMA_MAX_NK 1024
 
 struct LmAttn {
@@ -214,106 +193,35 @@ struct LmAttn {
     float scale;
 };
 
-// One workgroup = LMA_QT query rows of one (batch item, head); query row r of the q / out buffers sits at sequence position
-// q0 + r.  The four waves take LMA_RPW rows each and walk the keys in tiles of 64 staged in LDS (K padded to D + 1 words a
-// row: lane j reads row j), stopping after the tile that holds the workgroup's last position.  A cache row at or beyond Nk
-// is never loaded: its LDS slot is zero-filled and its weight is exactly 0, so whatever the cache holds there (stale rows,
-// NaN) cannot reach the output.  Per row and tile: lane j holds the score of key j (four interleaved partial dot products,
-// scaled by 1/sqrt(D)), keys j > position or behind the key mask have weight exactly 0, the tile's maximum and sum come from
-// butterflies, the running maximum m and sum l rescale the accumulator (flash-style), and the P.V product gives lane (g, d)
-// the keys j = g mod 64/D of output feature d; the 64/D partial accumulators are added after the last tile.  A tile without
-// an attended key is skipped; a row without one gives zeros.  Static LDS at D = 64: 38 KiB.
+// text_attn_tile.h's policy of the causal stack: row r of batch item b sits at b*bs + r*ld; query row r of the q / out
+// buffers is sequence position q0 + r and sees the keys j <= its position that the key mask leaves, so the key loop stops
+// after the tile that holds the workgroup's last position (< Nk).  Cache rows at or beyond Nk are never loaded: whatever
+// the cache holds there (stale rows, NaN) cannot reach the output.  The score is the dot product scaled by 1/sqrt(D).
+struct LmPolicy {
+    const float *q, *k, *v;
+    const int* mask;
+    float* out;
+    int ldq, ldk, ldv, ldo, rows, nkeys, q0;
+    float scale;
+    __device__ __forceinline__ LmPolicy(const LmAttn& p, int b, int h, int D) {
+        q = p.q + (size_t)b * (size_t)p.bsq + (size_t)h * D;
+        k = p.k + (size_t)b * (size_t)p.bsk + (size_t)h * D;
+        v = p.v + (size_t)b * (size_t)p.bsv + (size_t)h * D;
+        out = p.out + (size_t)b * (size_t)p.bso + (size_t)h * D;
+        mask = p.keymask ? p.keymask + (size_t)b * (size_t)p.bsm : nullptr;
+        ldq = p.ldq; ldk = p.ldk; ldv = p.ldv; ldo = p.ldo;
+        rows = p.Nq; nkeys = p.Nk; q0 = p.q0; scale = p.scale;
+    }
+    __device__ __forceinline__ int key_end(int i0) const { return q0 + min(i0 + TA_QT, rows); }
+    __device__ __forceinline__ bool skip(int i, int j0) const { return j0 > q0 + i; }      // the whole tile lies after this row
+    __device__ __forceinline__ bool valid(bool live, int i, int j) const { return live && j <= q0 + i; }
+    __device__ __forceinline__ float score(float dot, int, int) const { return dot * scale; }
+};
+
 template <int D>
-__global__ __launch_bounds__(64 * LM_WAVES) void lm_causal_attention_kernel(LmAttn p) {
-    __shared__ float qs[LMA_QT][D];
-    __shared__ float ks[LMA_KT][D + 1];
-    __shared__ float vs[LMA_KT][D];
-    __shared__ float ps[LM_WAVES][LMA_KT];
-    __shared__ int ms[LMA_KT];
-    constexpr int G = 64 / D;               // key groups of the P.V product
-    constexpr int D4 = D / 4;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int qt = blockIdx.x % p.qtiles;
-    const int h = (blockIdx.x / p.qtiles) % p.H;
-    const int b = blockIdx.x / (p.qtiles * p.H);
-    const int i0 = qt * LMA_QT, Nq = p.Nq, Nk = p.Nk;
-    const float* qb = p.q + (size_t)b * (size_t)p.bsq + (size_t)h * D;
-    const float* kb = p.k + (size_t)b * (size_t)p.bsk + (size_t)h * D;
-    const float* vb = p.v + (size_t)b * (size_t)p.bsv + (size_t)h * D;
-    float* ob = p.out + (size_t)b * (size_t)p.bso + (size_t)h * D;
-    const int* mb = p.keymask ? p.keymask + (size_t)b * (size_t)p.bsm : nullptr;
-
-    for (int e = tid; e < LMA_QT * D4; e += 64 * LM_WAVES) {
-        const int r = e / D4, c = e - r * D4;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i0 + r < Nq) a = ((const float4*)(qb + (size_t)(i0 + r) * (size_t)p.ldq))[c];
-        qs[r][4 * c] = a.x; qs[r][4 * c + 1] = a.y; qs[r][4 * c + 2] = a.z; qs[r][4 * c + 3] = a.w;
-    }
-    float m[LMA_RPW], l[LMA_RPW], acc[LMA_RPW];
-#pragma unroll
-    for (int rr = 0; rr < LMA_RPW; ++rr) { m[rr] = -INFINITY; l[rr] = 0.f; acc[rr] = 0.f; }
-    const int g = lane / D, d = lane - g * D;
-    const int last = p.q0 + min(i0 + LMA_QT, Nq) - 1;          // the last position of this workgroup's rows (< Nk)
-
-    for (int j0 = 0; j0 <= last; j0 += LMA_KT) {
-        __syncthreads();                                    // the previous tile's readers are done (first pass: nothing pending)
-        for (int e = tid; e < LMA_KT * D4; e += 64 * LM_WAVES) {
-            const int r = e / D4, c = e - r * D4;
-            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), bb = a;
-            if (j0 + r < Nk) {
-                a = ((const float4*)(kb + (size_t)(j0 + r) * (size_t)p.ldk))[c];
-                bb = ((const float4*)(vb + (size_t)(j0 + r) * (size_t)p.ldv))[c];
-            }
-            ks[r][4 * c] = a.x; ks[r][4 * c + 1] = a.y; ks[r][4 * c + 2] = a.z; ks[r][4 * c + 3] = a.w;
-            vs[r][4 * c] = bb.x; vs[r][4 * c + 1] = bb.y; vs[r][4 * c + 2] = bb.z; vs[r][4 * c + 3] = bb.w;
-        }
-        if (tid < LMA_KT) ms[tid] = (j0 + tid < Nk) && (mb == nullptr || mb[j0 + tid] != 0);
-        __syncthreads();
-        const bool live = ms[lane] != 0;
-#pragma unroll
-        for (int rr = 0; rr < LMA_RPW; ++rr) {
-            const int r = wave * LMA_RPW + rr;
-            if (i0 + r >= Nq) continue;                     // (wave-uniform)
-            const int pos = p.q0 + i0 + r;
-            if (j0 > pos) continue;                         // the whole tile lies after this row (wave-uniform)
-            const bool valid = live && (j0 + lane <= pos);
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-            for (int dd = 0; dd < D; dd += 4) {
-                s0 = fmaf(qs[r][dd], ks[lane][dd], s0);
-                s1 = fmaf(qs[r][dd + 1], ks[lane][dd + 1], s1);
-                s2 = fmaf(qs[r][dd + 2], ks[lane][dd + 2], s2);
-                s3 = fmaf(qs[r][dd + 3], ks[lane][dd + 3], s3);
-            }
-            float sc = -INFINITY;
-            if (valid) sc = ((s0 + s1) + (s2 + s3)) * p.scale;
-            const float mt = lm_wave_max(sc);
-            if (mt == -INFINITY) continue;                  // no attended key in this tile (wave-uniform)
-            const float mn = fmaxf(m[rr], mt);
-            const float alpha = expf(m[rr] - mn);           // first attended tile: exp(-inf) = 0
-            const float pj = valid ? expf(sc - mn) : 0.f;
-            l[rr] = l[rr] * alpha + lm_wave_sum(pj);
-            m[rr] = mn;
-            __builtin_amdgcn_wave_barrier();                // the previous row's reads of ps[wave] are issued (LDS is in order)
-            ps[wave][lane] = pj;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            float a = 0.f;
-#pragma unroll 8
-            for (int jj = 0; jj < LMA_KT / G; ++jj) a = fmaf(ps[wave][jj * G + g], vs[jj * G + g][d], a);
-            acc[rr] = acc[rr] * alpha + a;
-        }
-    }
-#pragma unroll
-    for (int rr = 0; rr < LMA_RPW; ++rr) {
-        const int i = i0 + wave * LMA_RPW + rr;
-        if (i >= Nq) continue;
-        float a = acc[rr];
-#pragma unroll
-        for (int o = D; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
-        if (lane < D) ob[(size_t)i * (size_t)p.ldo + lane] = l[rr] > 0.f ? a / l[rr] : 0.f;
-    }
+__global__ __launch_bounds__(64 * TA_WAVES) void lm_causal_attention_kernel(LmAttn p) {
+    typedef LmPolicy Policy;
+#include "text_attn_body.inc"
 }
 
 // slots: p0=q p1=k p2=v p3=keymask int32 (nullable: no key masked; 0 = masked; key j of batch item b at b*bsm + j) p4=out
@@ -330,16 +238,12 @@ int launch_causal_attention(const aed_op* op, hipStream_t s) {
     p.bsq = op->i[9]; p.bsk = op->i[10]; p.bsv = op->i[11]; p.bso = op->i[12]; p.bsm = op->i[13];
     AED_REQUIRE(p.q && p.k && p.v && p.out, "causal_attention: null pointer (q %p, k %p, v %p, out %p)", (const void*)p.q,
                 (const void*)p.k, (const void*)p.v, (void*)p.out);
-    AED_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64, "causal_attention: head size %d, supported 8, 16, 32, 64", D);
+    TEXT_ATTN_REQUIRE_HEAD("causal_attention", D);
     AED_REQUIRE(p.Nq >= 1 && p.q0 >= 0 && (long long)p.q0 + p.Nq <= LMA_MAX_NK,
                 "causal_attention: Nq %d rows from position %d: Nk = q0 + Nq outside [1, %d]", p.Nq, p.q0, LMA_MAX_NK);
     p.Nk = p.q0 + p.Nq;
-    AED_REQUIRE(p.B >= 1 && p.H >= 1, "causal_attention: B %d and H %d must be positive", p.B, p.H);
     const long long hd = (long long)p.H * D;
-    AED_REQUIRE(p.ldq >= hd && p.ldk >= hd && p.ldv >= hd && p.ldo >= hd && p.ldq % 4 == 0 && p.ldk % 4 == 0 && p.ldv % 4 == 0 &&
-                    p.ldo % 4 == 0,
-                "causal_attention: row strides (q %d, k %d, v %d, out %d) must be multiples of 4 and at least H*D = %lld", p.ldq,
-                p.ldk, p.ldv, p.ldo, hd);
+    TEXT_ATTN_REQUIRE_STRIDES("causal_attention", p, hd);
     AED_REQUIRE(p.bsq >= 0 && p.bsk >= 0 && p.bsv >= 0 && p.bso >= 0 && p.bsq % 4 == 0 && p.bsk % 4 == 0 && p.bsv % 4 == 0 && p.bso % 4 == 0 &&
                     (p.B == 1 || p.bso >= (long long)(p.Nq - 1) * p.ldo + hd),
                 "causal_attention: batch strides (q %lld, k %lld, v %lld, out %lld) must be non-negative multiples of 4, out's at "
@@ -347,18 +251,7 @@ int launch_causal_attention(const aed_op* op, hipStream_t s) {
                 p.bsq, p.bsk, p.bsv, p.bso);
     AED_REQUIRE(p.keymask == nullptr || p.bsm >= p.Nk || p.B == 1, "causal_attention: key-mask batch stride %lld below Nk = %d",
                 p.bsm, p.Nk);
-    AED_REQUIRE(lm_aligned16(p.q) && lm_aligned16(p.k) && lm_aligned16(p.v), "causal_attention: q, k and v must be 16-byte aligned");
+    AED_REQUIRE(aed_aligned16(p.q) && aed_aligned16(p.k) && aed_aligned16(p.v), "causal_attention: q, k and v must be 16-byte aligned");
     p.scale = 1.0f / sqrtf((float)D);
-    p.qtiles = (p.Nq + LMA_QT - 1) / LMA_QT;
-    const long long blocks = (long long)p.qtiles * p.H * p.B;
-    AED_REQUIRE(blocks < (1LL << 31), "causal_attention: B %d x H %d x Nq %d is too large for one launch", p.B, p.H, p.Nq);
-    const dim3 grid((unsigned)blocks), block(64 * LM_WAVES);
-    switch (D) {
-        case 8: hipLaunchKernelGGL(lm_causal_attention_kernel<8>, grid, block, 0, s, p); break;
-        case 16: hipLaunchKernelGGL(lm_causal_attention_kernel<16>, grid, block, 0, s, p); break;
-        case 32: hipLaunchKernelGGL(lm_causal_attention_kernel<32>, grid, block, 0, s, p); break;
-        default: hipLaunchKernelGGL(lm_causal_attention_kernel<64>, grid, block, 0, s, p); break;
-    }
-    AED_CHECK_HIP(hipGetLastError());
-    return 0;
+    TEXT_ATTN_LAUNCH("causal_attention", lm_causal_attention_kernel, p, D, p.Nq, "Nq", s);
 }

@@ -6,21 +6,11 @@
 // All fp32, wave64, no atomics; every sum runs in a fixed order (lane-strided partial sums, then an xor butterfly over the
 // wave, whose two operands commute), so a launch is bit-repeatable.  The text encoder is a few hundred tokens wide: these
 // kernels are latency- and bandwidth-bound, and the contractions of the attention (D <= 64, L <= 512) stay on the vector ALU.
-#include "aed_common.h"
+// The attention is the tile body of text_attn_tile.h under T5Policy (lm.hip runs the same body causally); the wave
+// butterflies, gelu_new and the launchers' small helpers are those of rows_common.h, shared with lm.hip.
+#include "text_attn_tile.h"
 
-#define T5_WAVES 4                          // waves per workgroup of every kernel in this file (256 threads)
-
-__device__ __forceinline__ float t5_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float t5_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-static inline bool t5_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+#define T5_WAVES 4                          // waves per workgroup of the one-wave-per-row kernels (256 threads)
 
 // ------------------------------------------------------------------------------------ embedding gather
 // One wave per output row.  The host range-checks the ids before upload; an id outside the table still reads nothing
@@ -44,7 +34,7 @@ int launch_t5_embed(const aed_op* op, hipStream_t s) {
     const float* table = (const float*)op->p[0];
     const int* ids = (const int*)op->p[1];
     float* out = (float*)op->p[2];
-    const long long rows = (long long)((uint64_t)(uint32_t)op->i[0] | ((uint64_t)(uint32_t)op->i[1] << 32));
+    const long long rows = aed_rows64(op);
     const int width = op->i[2], vocab = op->i[3], ldo = op->i[4];
     AED_REQUIRE(table && ids && out, "t5_embed: null pointer (table %p, ids %p, out %p)", (const void*)table, (const void*)ids,
                 (void*)out);
@@ -52,7 +42,7 @@ int launch_t5_embed(const aed_op* op, hipStream_t s) {
     AED_REQUIRE(vocab > 0, "t5_embed: vocab %d must be positive", vocab);
     AED_REQUIRE(width > 0 && width % 4 == 0, "t5_embed: width %d must be a positive multiple of 4", width);
     AED_REQUIRE(ldo >= width && ldo % 4 == 0, "t5_embed: ldo %d must be a multiple of 4 and at least the width %d", ldo, width);
-    AED_REQUIRE(t5_aligned16(table) && t5_aligned16(out), "t5_embed: table and out must be 16-byte aligned");
+    AED_REQUIRE(aed_aligned16(table) && aed_aligned16(out), "t5_embed: table and out must be 16-byte aligned");
     hipLaunchKernelGGL(t5_embed_kernel, dim3((unsigned)((rows + T5_WAVES - 1) / T5_WAVES)), dim3(64 * T5_WAVES), 0, s, table, ids,
                        out, rows, width, vocab, ldo);
     AED_CHECK_HIP(hipGetLastError());
@@ -77,7 +67,7 @@ __global__ __launch_bounds__(64 * T5_WAVES) void t5_rmsnorm_kernel(const float* 
         const float4 a = xr[v];
         ss += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
     }
-    ss = t5_wave_sum(ss);
+    ss = aed_wave_sum(ss);
     const float r = 1.0f / sqrtf(ss / (float)width + eps);
     for (int v = lane; v < n4; v += 64) {
         const float4 a = xr[v], g = wr[v];
@@ -91,7 +81,7 @@ int launch_rmsnorm(const aed_op* op, hipStream_t s) {
     const float* x = (const float*)op->p[0];
     const float* w = (const float*)op->p[1];
     float* y = (float*)op->p[2];
-    const long long rows = (long long)((uint64_t)(uint32_t)op->i[0] | ((uint64_t)(uint32_t)op->i[1] << 32));
+    const long long rows = aed_rows64(op);
     const int width = op->i[2], ldx = op->i[3], ldy = op->i[4];
     const float eps = op->f[0];
     AED_REQUIRE(x && w && y, "rmsnorm: null pointer (x %p, w %p, y %p)", (const void*)x, (const void*)w, (void*)y);
@@ -100,7 +90,7 @@ int launch_rmsnorm(const aed_op* op, hipStream_t s) {
     AED_REQUIRE(ldx >= width && ldx % 4 == 0 && ldy >= width && ldy % 4 == 0,
                 "rmsnorm: row strides (ldx %d, ldy %d) must be multiples of 4 and at least the width %d", ldx, ldy, width);
     AED_REQUIRE(eps >= 0.f, "rmsnorm: eps %g must not be negative", (double)eps);
-    AED_REQUIRE(t5_aligned16(x) && t5_aligned16(w) && t5_aligned16(y), "rmsnorm: x, w and y must be 16-byte aligned");
+    AED_REQUIRE(aed_aligned16(x) && aed_aligned16(w) && aed_aligned16(y), "rmsnorm: x, w and y must be 16-byte aligned");
     hipLaunchKernelGGL(t5_rmsnorm_kernel, dim3((unsigned)((rows + T5_WAVES - 1) / T5_WAVES)), dim3(64 * T5_WAVES), 0, s, x, w, y,
                        rows, width, ldx, ldy, eps);
     AED_CHECK_HIP(hipGetLastError());
@@ -108,10 +98,6 @@ int launch_rmsnorm(const aed_op* op, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------ gated activation
-__device__ __forceinline__ float t5_gelu_new(float x) {
-    return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
-}
-
 __global__ __launch_bounds__(256) void t5_gated_act_kernel(const float* __restrict__ in, float* __restrict__ out, long long rows,
                                                            int F, int ld_in, int ld_out) {
     const int f4 = F / 4;
@@ -122,7 +108,7 @@ __global__ __launch_bounds__(256) void t5_gated_act_kernel(const float* __restri
         const float4* ir = (const float4*)(in + (size_t)r * (size_t)ld_in);
         const float4 a = ir[c], b = ir[f4 + c];
         ((float4*)(out + (size_t)r * (size_t)ld_out))[c] =
-            make_float4(t5_gelu_new(a.x) * b.x, t5_gelu_new(a.y) * b.y, t5_gelu_new(a.z) * b.z, t5_gelu_new(a.w) * b.w);
+            make_float4(aed_gelu_new(a.x) * b.x, aed_gelu_new(a.y) * b.y, aed_gelu_new(a.z) * b.z, aed_gelu_new(a.w) * b.w);
     }
 }
 
@@ -131,14 +117,14 @@ __global__ __launch_bounds__(256) void t5_gated_act_kernel(const float* __restri
 int launch_gated_act(const aed_op* op, hipStream_t s) {
     const float* in = (const float*)op->p[0];
     float* out = (float*)op->p[1];
-    const long long rows = (long long)((uint64_t)(uint32_t)op->i[0] | ((uint64_t)(uint32_t)op->i[1] << 32));
+    const long long rows = aed_rows64(op);
     const int F = op->i[2], ld_in = op->i[3], ld_out = op->i[4];
     AED_REQUIRE(in && out, "gated_act: null pointer (in %p, out %p)", (const void*)in, (void*)out);
     AED_REQUIRE(rows > 0 && rows <= (1LL << 32), "gated_act: rows %lld outside [1, 2^32]", rows);
     AED_REQUIRE(F > 0 && F % 4 == 0 && F <= (1 << 28), "gated_act: F %d must be a positive multiple of 4", F);
     AED_REQUIRE(ld_in >= 2 * F && ld_in % 4 == 0, "gated_act: ld_in %d must be a multiple of 4 and at least 2 F = %d", ld_in, 2 * F);
     AED_REQUIRE(ld_out >= F && ld_out % 4 == 0, "gated_act: ld_out %d must be a multiple of 4 and at least F = %d", ld_out, F);
-    AED_REQUIRE(t5_aligned16(in) && t5_aligned16(out), "gated_act: in and out must be 16-byte aligned");
+    AED_REQUIRE(aed_aligned16(in) && aed_aligned16(out), "gated_act: in and out must be 16-byte aligned");
     const long long blocks = (rows * (F / 4) + 255) / 256;
     const long long cap = 256LL * 8;
     hipLaunchKernelGGL(t5_gated_act_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, s, in, out, rows, F, ld_in,
@@ -148,10 +134,6 @@ int launch_gated_act(const aed_op* op, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------ attention with a relative-position bias
-#define T5A_QT 16                           // query rows per workgroup (T5A_QT / T5_WAVES per wave)
-#define T5A_KT 64                           // keys per tile: one per lane
-#define T5A_RPW (T5A_QT / T5_WAVES)
-
 struct T5Attn {
     const float *q, *k, *v, *pos;
     const int* keymask;                     // nullable: every key attended
@@ -159,96 +141,34 @@ struct T5Attn {
     int B, H, L, ldq, ldk, ldv, ldo, qtiles;
 };
 
-// One workgroup = T5A_QT query rows of one (batch item, head); its four waves take T5A_RPW rows each and walk the keys in
-// tiles of 64 staged in LDS (K padded to D + 1 words a row: lane j reads row j).  Per row and tile: lane j holds the score of
-// key j (four interleaved partial dot products), the tile's maximum and sum come from butterflies, the running maximum m
-// and sum l rescale the accumulator (flash-style), and the P.V product gives lane (g, d) the keys j = g mod 64/D of output
-// feature d; the 64/D partial accumulators are added after the last tile.  A masked key has weight exactly 0; a tile
-// without an attended key is skipped.  Static LDS at D = 64: 38 KiB, four workgroups to a CU.
+// text_attn_tile.h's policy of the T5 encoder: row i of batch item b is row b*L + i of a flat buffer, every query row sees
+// all L keys (but those behind the key mask), and the score is the raw dot product plus pos[h][j - i + L - 1].
+struct T5Policy {
+    const float *q, *k, *v, *posh;
+    const int* mask;
+    float* out;
+    int ldq, ldk, ldv, ldo, rows, nkeys;
+    __device__ __forceinline__ T5Policy(const T5Attn& p, int b, int h, int D) {
+        const size_t row0 = (size_t)b * (size_t)p.L, col = (size_t)h * D;
+        q = p.q + row0 * (size_t)p.ldq + col;
+        k = p.k + row0 * (size_t)p.ldk + col;
+        v = p.v + row0 * (size_t)p.ldv + col;
+        out = p.out + row0 * (size_t)p.ldo + col;
+        mask = p.keymask ? p.keymask + row0 : nullptr;
+        posh = p.pos + (size_t)h * (size_t)(2 * p.L - 1);
+        ldq = p.ldq; ldk = p.ldk; ldv = p.ldv; ldo = p.ldo;
+        rows = nkeys = p.L;
+    }
+    __device__ __forceinline__ int key_end(int) const { return rows; }
+    __device__ __forceinline__ bool skip(int, int) const { return false; }
+    __device__ __forceinline__ bool valid(bool live, int, int) const { return live; }
+    __device__ __forceinline__ float score(float dot, int i, int j) const { return dot + posh[j - i + rows - 1]; }
+};
+
 template <int D>
-__global__ __launch_bounds__(64 * T5_WAVES) void t5_attention_kernel(T5Attn p) {
-    __shared__ float qs[T5A_QT][D];
-    __shared__ float ks[T5A_KT][D + 1];
-    __shared__ float vs[T5A_KT][D];
-    __shared__ float ps[T5_WAVES][T5A_KT];
-    __shared__ int ms[T5A_KT];
-    constexpr int G = 64 / D;               // key groups of the P.V product
-    constexpr int D4 = D / 4;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int qt = blockIdx.x % p.qtiles;
-    const int h = (blockIdx.x / p.qtiles) % p.H;
-    const int b = blockIdx.x / (p.qtiles * p.H);
-    const int i0 = qt * T5A_QT, L = p.L;
-    const size_t row0 = (size_t)b * (size_t)L;
-    const float* posh = p.pos + (size_t)h * (size_t)(2 * L - 1);
-
-    for (int e = tid; e < T5A_QT * D4; e += 64 * T5_WAVES) {
-        const int r = e / D4, c = e - r * D4;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i0 + r < L) a = ((const float4*)(p.q + (row0 + i0 + r) * (size_t)p.ldq + (size_t)h * D))[c];
-        qs[r][4 * c] = a.x; qs[r][4 * c + 1] = a.y; qs[r][4 * c + 2] = a.z; qs[r][4 * c + 3] = a.w;
-    }
-    float m[T5A_RPW], l[T5A_RPW], acc[T5A_RPW];
-#pragma unroll
-    for (int rr = 0; rr < T5A_RPW; ++rr) { m[rr] = -INFINITY; l[rr] = 0.f; acc[rr] = 0.f; }
-    const int g = lane / D, d = lane - g * D;
-
-    for (int j0 = 0; j0 < L; j0 += T5A_KT) {
-        __syncthreads();                                    // the previous tile's readers are done (first pass: nothing pending)
-        for (int e = tid; e < T5A_KT * D4; e += 64 * T5_WAVES) {
-            const int r = e / D4, c = e - r * D4;
-            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), bb = a;
-            if (j0 + r < L) {
-                a = ((const float4*)(p.k + (row0 + j0 + r) * (size_t)p.ldk + (size_t)h * D))[c];
-                bb = ((const float4*)(p.v + (row0 + j0 + r) * (size_t)p.ldv + (size_t)h * D))[c];
-            }
-            ks[r][4 * c] = a.x; ks[r][4 * c + 1] = a.y; ks[r][4 * c + 2] = a.z; ks[r][4 * c + 3] = a.w;
-            vs[r][4 * c] = bb.x; vs[r][4 * c + 1] = bb.y; vs[r][4 * c + 2] = bb.z; vs[r][4 * c + 3] = bb.w;
-        }
-        if (tid < T5A_KT) ms[tid] = (j0 + tid < L) && (p.keymask == nullptr || p.keymask[row0 + j0 + tid] != 0);
-        __syncthreads();
-        const bool valid = ms[lane] != 0;
-#pragma unroll
-        for (int rr = 0; rr < T5A_RPW; ++rr) {
-            const int r = wave * T5A_RPW + rr, i = i0 + r;
-            if (i >= L) continue;                           // (wave-uniform)
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-            for (int dd = 0; dd < D; dd += 4) {
-                s0 = fmaf(qs[r][dd], ks[lane][dd], s0);
-                s1 = fmaf(qs[r][dd + 1], ks[lane][dd + 1], s1);
-                s2 = fmaf(qs[r][dd + 2], ks[lane][dd + 2], s2);
-                s3 = fmaf(qs[r][dd + 3], ks[lane][dd + 3], s3);
-            }
-            float sc = -INFINITY;
-            if (valid) sc = ((s0 + s1) + (s2 + s3)) + posh[(j0 + lane) - i + L - 1];
-            const float mt = t5_wave_max(sc);
-            if (mt == -INFINITY) continue;                  // no attended key in this tile (wave-uniform)
-            const float mn = fmaxf(m[rr], mt);
-            const float alpha = expf(m[rr] - mn);           // first attended tile: exp(-inf) = 0
-            const float pj = valid ? expf(sc - mn) : 0.f;
-            l[rr] = l[rr] * alpha + t5_wave_sum(pj);
-            m[rr] = mn;
-            __builtin_amdgcn_wave_barrier();                // the previous row's reads of ps[wave] are issued (LDS is in order)
-            ps[wave][lane] = pj;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            float a = 0.f;
-#pragma unroll 8
-            for (int jj = 0; jj < T5A_KT / G; ++jj) a = fmaf(ps[wave][jj * G + g], vs[jj * G + g][d], a);
-            acc[rr] = acc[rr] * alpha + a;
-        }
-    }
-#pragma unroll
-    for (int rr = 0; rr < T5A_RPW; ++rr) {
-        const int i = i0 + wave * T5A_RPW + rr;
-        if (i >= L) continue;
-        float a = acc[rr];
-#pragma unroll
-        for (int o = D; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
-        if (lane < D) p.out[(row0 + i) * (size_t)p.ldo + (size_t)h * D + lane] = l[rr] > 0.f ? a / l[rr] : 0.f;
-    }
+__global__ __launch_bounds__(64 * TA_WAVES) void t5_attention_kernel(T5Attn p) {
+    typedef T5Policy Policy;
+#include "text_attn_body.inc"
 }
 
 // slots: p0=q p1=k p2=v (row b*L + i of a [B*L][ld] buffer, head h in columns [h*D, (h+1)*D))  p3=pos float[H][2L-1]
@@ -263,25 +183,10 @@ int launch_t5_attention(const aed_op* op, hipStream_t s) {
     p.ldq = op->i[4]; p.ldk = op->i[5]; p.ldv = op->i[6]; p.ldo = op->i[7];
     AED_REQUIRE(p.q && p.k && p.v && p.pos && p.out, "t5_attention: null pointer (q %p, k %p, v %p, pos %p, out %p)",
                 (const void*)p.q, (const void*)p.k, (const void*)p.v, (const void*)p.pos, (void*)p.out);
-    AED_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64, "t5_attention: head size %d, supported 8, 16, 32, 64", D);
+    TEXT_ATTN_REQUIRE_HEAD("t5_attention", D);
     AED_REQUIRE(p.L >= 1 && p.L <= 512, "t5_attention: L %d outside [1, 512]", p.L);
-    AED_REQUIRE(p.B >= 1 && p.H >= 1, "t5_attention: B %d and H %d must be positive", p.B, p.H);
     const long long hd = (long long)p.H * D;
-    AED_REQUIRE(p.ldq >= hd && p.ldk >= hd && p.ldv >= hd && p.ldo >= hd && p.ldq % 4 == 0 && p.ldk % 4 == 0 && p.ldv % 4 == 0 &&
-                    p.ldo % 4 == 0,
-                "t5_attention: row strides (q %d, k %d, v %d, out %d) must be multiples of 4 and at least H*D = %lld", p.ldq,
-                p.ldk, p.ldv, p.ldo, hd);
-    AED_REQUIRE(t5_aligned16(p.q) && t5_aligned16(p.k) && t5_aligned16(p.v), "t5_attention: q, k and v must be 16-byte aligned");
-    p.qtiles = (p.L + T5A_QT - 1) / T5A_QT;
-    const long long blocks = (long long)p.qtiles * p.H * p.B;
-    AED_REQUIRE(blocks < (1LL << 31), "t5_attention: B %d x H %d x L %d is too large for one launch", p.B, p.H, p.L);
-    const dim3 grid((unsigned)blocks), block(64 * T5_WAVES);
-    switch (D) {
-        case 8: hipLaunchKernelGGL(t5_attention_kernel<8>, grid, block, 0, s, p); break;
-        case 16: hipLaunchKernelGGL(t5_attention_kernel<16>, grid, block, 0, s, p); break;
-        case 32: hipLaunchKernelGGL(t5_attention_kernel<32>, grid, block, 0, s, p); break;
-        default: hipLaunchKernelGGL(t5_attention_kernel<64>, grid, block, 0, s, p); break;
-    }
-    AED_CHECK_HIP(hipGetLastError());
-    return 0;
+    TEXT_ATTN_REQUIRE_STRIDES("t5_attention", p, hd);
+    AED_REQUIRE(aed_aligned16(p.q) && aed_aligned16(p.k) && aed_aligned16(p.v), "t5_attention: q, k and v must be 16-byte aligned");
+    TEXT_ATTN_LAUNCH("t5_attention", t5_attention_kernel, p, D, p.L, "L", s);
 }

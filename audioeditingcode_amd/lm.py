@@ -22,14 +22,11 @@ in the caches before any attention reads them; the decode passes keep their one 
 and write q|k|v straight into the cache row.  `NativeGPT2` fills the `language_model` slot of `text_encoders.TextEncoders`.
 Dropout is absent: eval mode only.
 """
-import collections
-from types import SimpleNamespace
-
 import torch
 
 from . import _lib as L
-from . import tape as tape_mod
 from .tape import Tape
+from .tape_engine import NativeTextModule, TapeEngine, config_dict
 
 _CONFIG_DEFAULTS = dict(n_embd=768, n_head=12, n_layer=12, n_positions=1024, n_inner=None, layer_norm_epsilon=1e-5,
                         activation_function="gelu_new", scale_attn_weights=True, scale_attn_by_inverse_layer_idx=False,
@@ -38,22 +35,17 @@ _CONFIG_DEFAULTS = dict(n_embd=768, n_head=12, n_layer=12, n_positions=1024, n_i
 
 def _config_dict(config):
     """The fields the stack reads, from a transformers GPT2Config, any object with those attributes, or a dict (config.json)."""
-    get = config.get if isinstance(config, dict) else lambda k, d=None: getattr(config, k, d)
-    out = {k: (get(k, d) if get(k, d) is not None else d) for k, d in _CONFIG_DEFAULTS.items()}
-    for k in ("n_embd", "n_head", "n_layer", "n_positions"):
-        out[k] = int(out[k])
+    out = config_dict(config, _CONFIG_DEFAULTS, ("n_embd", "n_head", "n_layer", "n_positions"))
     out["n_inner"] = int(out["n_inner"]) if out["n_inner"] is not None else 4 * out["n_embd"]
     return out
 
 
-class GPT2Engine:
+class GPT2Engine(TapeEngine):
     """A Hugging Face GPT2Model (state dict + config) on the op tape.  `generate(inputs_embeds, attention_mask, n)` -> the n
-    generated states [B, n, n_embd], fp32 on the device."""
-
-    MAX_SHAPES = 4              # (B, P, n) plans kept (tape + activations + caches + one instantiated hipGraph each)
+    generated states [B, n, n_embd], fp32 on the device.  One plan per (B, P, n); a plan holds the layers' caches too."""
 
     def __init__(self, config, state_dict, device):
-        self.device = torch.device(device)
+        super().__init__(device)
         cfg = self.cfg = _config_dict(config)
         who = "GPT2Engine"
         if cfg["activation_function"] != "gelu_new":
@@ -74,21 +66,10 @@ class GPT2Engine:
         self.d, self.H, self.D, self.inner, self.n_layers = d, H, d // H, cfg["n_inner"], cfg["n_layer"]
         self.n_positions, self.eps = cfg["n_positions"], float(cfg["layer_norm_epsilon"])
         self._pack(state_dict)
-        self.stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
-        self._plans = collections.OrderedDict()
 
     # ------------------------------------------------------------------ weights
     def _pack(self, sd):
-        def get(name):
-            for n in (name, "transformer." + name):
-                if n in sd:
-                    return sd[n].detach().to(torch.float32)
-            raise L.AedError(f"GPT2Engine: the state dict has no '{name}'")
-
-        def put(t, shape):
-            if tuple(t.shape) != tuple(shape):
-                raise L.AedError(f"GPT2Engine: a weight has shape {tuple(t.shape)}, the config says {tuple(shape)}")
-            return t.contiguous().to(self.device)
+        get, put = lambda name: self._get(sd, name, "transformer." + name), self._put      # noqa: E731
 
         def conv1d(name, k, n):
             """transformers' Conv1D keeps [in, out]; the tape's GEMM reads [N, K] = [out, in]."""
@@ -105,11 +86,6 @@ class GPT2Engine:
             w[f"{i}.fc"], w[f"{i}.fc.b"] = conv1d(b + "mlp.c_fc", d, inner)
             w[f"{i}.proj"], w[f"{i}.proj.b"] = conv1d(b + "mlp.c_proj", inner, d)
         w["ln_f.g"], w["ln_f.b"] = put(get("ln_f.weight"), (d,)), put(get("ln_f.bias"), (d,))
-
-    @property
-    def weight_bytes(self):
-        """Device memory of the packed weights."""
-        return sum(t.numel() * t.element_size() for t in self.w.values())
 
     # ------------------------------------------------------------------ the tape of one (B, P, n)
     def _check_shape(self, B, P, n):
@@ -172,18 +148,6 @@ class GPT2Engine:
             tp.layernorm_rows(hd, w["ln_f.g"], w["ln_f.b"], gen[:, k, :], rows=B, width=d, eps=self.eps, name=f"d{k}.ln_f")
         return dict(tape=tp, x=x, mask=mask, gen=gen, caches=caches, B=B, P=P, n=n, graph=False)
 
-    def _plan(self, B, P, n):
-        key = (B, P, n, getattr(tape_mod._regime, "arith", None) or tape_mod.DEFAULT_ARITH)
-        plan = self._plans.pop(key, None)
-        if plan is None:
-            while len(self._plans) >= self.MAX_SHAPES:
-                if self.stream is not None:
-                    torch.cuda.synchronize(self.device)         # an evicted plan's graph may still be in flight
-                self._plans.popitem(last=False)                 # (its Tape destroys the graph)
-            plan = self.build_plan(B, P, n)
-        self._plans[key] = plan                                 # most recently used last
-        return plan
-
     # ------------------------------------------------------------------ run
     def check_inputs(self, inputs_embeds, attention_mask=None, n=8):
         """Host-side refusals; returns (inputs_embeds, mask int32 [B, P] on the host).  The mask is read on the host (a row
@@ -212,59 +176,23 @@ class GPT2Engine:
     @torch.inference_mode()
     def generate(self, inputs_embeds, attention_mask=None, n=8, use_graph=True):
         x, mask = self.check_inputs(inputs_embeds, attention_mask, n)
-        if self.device.type != "cuda":
-            raise L.AedError(f"GPT2Engine on device={self.device} builds tapes only; running needs an MI355X (HIP) -- "
-                             f"there is no CPU fallback")
+        self._require_gpu()
         B, P = x.shape[:2]
+
+        def fill(plan):
+            plan["x"][:, :P].copy_(x.detach())
+            plan["mask"][:, :P].copy_(mask)
         with torch.cuda.device(self.device):
             plan = self._plan(B, P, int(n))
-            tp = plan["tape"]
-            cur = torch.cuda.current_stream(self.device)
-            self.stream.wait_stream(cur)
-            with torch.cuda.stream(self.stream):
-                plan["x"][:, :P].copy_(x.detach())
-                plan["mask"][:, :P].copy_(mask)
-                if not use_graph:
-                    tp.run()
-                else:
-                    if not plan["graph"]:
-                        tp.run()                                # once outside capture: a refused record raises here
-                        tp.capture()
-                        plan["graph"] = True
-                    tp.replay()
-            cur.wait_stream(self.stream)
+            self._run(plan, fill, use_graph)
             return plan["gen"].clone()
 
 
-class NativeGPT2:
+class NativeGPT2(NativeTextModule):
     """Fills the `language_model` slot of `text_encoders.TextEncoders`: `generate_states(inputs_embeds, attention_mask, n)`
     returns the n generated states of AudioLDM2's continuous autoregression, computed by a GPT2Engine."""
 
-    def __init__(self, engine, config=None):
-        self.engine = engine
-        if config is None or isinstance(config, dict):
-            config = SimpleNamespace(**{"model_type": "gpt2", **(config or engine.cfg)})
-        self.config = config
-
-    @classmethod
-    def from_module(cls, hf_module, device):
-        """From a live transformers GPT2Model (its state dict is copied; the module itself is not kept)."""
-        return cls(GPT2Engine(hf_module.config, hf_module.state_dict(), device), hf_module.config)
-
-    @classmethod
-    def from_pretrained(cls, path, device):
-        """From a checkpoint directory (config.json + model.safetensors | sharded safetensors | pytorch_model.bin) without
-        building a torch module."""
-        from .t5 import read_checkpoint
-        cfg, sd = read_checkpoint(path)
-        cfg.setdefault("model_type", "gpt2")
-        return cls(GPT2Engine(cfg, sd, device), SimpleNamespace(**cfg))
-
-    def parameters(self):
-        return iter(self.engine.w.values())
-
-    def eval(self):
-        return self
+    ENGINE, MODEL_TYPE = GPT2Engine, "gpt2"
 
     def generate_states(self, inputs_embeds, attention_mask=None, n=8):
         return self.engine.generate(inputs_embeds, attention_mask, n)

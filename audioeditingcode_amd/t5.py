@@ -11,31 +11,19 @@ captured as a hipGraph: the project's GEMM kernels (under the caller's `tape.ari
 vendor BLAS and no per-kernel Python.  `NativeT5Encoder` wraps an engine in the call signature of `transformers.T5EncoderModel`
 that `text_encoders.TextEncoders` uses.  Dropout is absent: the encoders run in eval mode only.
 """
-import collections
-import json
 import math
-import os
-from types import SimpleNamespace
 
 import torch
 
 from . import _lib as L
-from . import tape as tape_mod
 from .tape import Tape
+from .tape_engine import NativeTextModule, TapeEngine, config_dict, read_checkpoint  # noqa: F401  (read_checkpoint: re-export)
 
 _CONFIG_DEFAULTS = dict(vocab_size=32128, d_model=512, d_kv=64, d_ff=2048, num_layers=6, num_heads=8,
                         relative_attention_num_buckets=32, relative_attention_max_distance=128, layer_norm_epsilon=1e-6,
                         feed_forward_proj="relu", is_decoder=False)
-
-
-def _config_dict(config):
-    """The fields the encoder reads, from a transformers T5Config, any object with those attributes, or a dict (config.json)."""
-    get = config.get if isinstance(config, dict) else lambda k, d=None: getattr(config, k, d)
-    out = {k: (get(k, d) if get(k, d) is not None else d) for k, d in _CONFIG_DEFAULTS.items()}
-    for k in ("vocab_size", "d_model", "d_kv", "d_ff", "num_layers", "num_heads", "relative_attention_num_buckets",
-              "relative_attention_max_distance"):
-        out[k] = int(out[k])
-    return out
+_CONFIG_INTS = ("vocab_size", "d_model", "d_kv", "d_ff", "num_layers", "num_heads", "relative_attention_num_buckets",
+                "relative_attention_max_distance")
 
 
 def relative_position_bucket(delta, num_buckets=32, max_distance=128):
@@ -68,38 +56,13 @@ def _activation(feed_forward_proj):
     raise L.AedError(f"T5EncoderEngine: feed_forward_proj {name!r} is not supported (relu, gated-gelu / gated-gelu_new)")
 
 
-def read_checkpoint(path):
-    """(config dict, state dict on the host) of a checkpoint directory: config.json + model.safetensors | sharded safetensors |
-    pytorch_model.bin, without building a torch module."""
-    with open(os.path.join(path, "config.json")) as f:
-        cfg = json.load(f)
-    sd = {}
-    index = os.path.join(path, "model.safetensors.index.json")
-    single = os.path.join(path, "model.safetensors")
-    if os.path.exists(single) or os.path.exists(index):
-        from safetensors.torch import load_file
-        files = [single]
-        if not os.path.exists(single):
-            with open(index) as f:
-                files = sorted({os.path.join(path, v) for v in json.load(f)["weight_map"].values()})
-        for fn in files:
-            sd.update(load_file(fn))
-    elif os.path.exists(os.path.join(path, "pytorch_model.bin")):
-        sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
-    else:
-        raise FileNotFoundError(f"{path}: no model.safetensors, model.safetensors.index.json or pytorch_model.bin")
-    return {k: v for k, v in cfg.items() if not k.startswith("_")}, sd
-
-
-class T5EncoderEngine:
+class T5EncoderEngine(TapeEngine):
     """A Hugging Face T5 encoder (state dict + config) on the op tape.  `encode(input_ids, attention_mask)` -> the last hidden
-    state [B, L, d_model], fp32 on the device; padded positions are computed too, as transformers does."""
-
-    MAX_SHAPES = 4              # (B, L) plans kept (tape + activations + one instantiated hipGraph each; weights are shared)
+    state [B, L, d_model], fp32 on the device; padded positions are computed too, as transformers does.  One plan per (B, L)."""
 
     def __init__(self, config, state_dict, device):
-        self.device = torch.device(device)
-        cfg = self.cfg = _config_dict(config)
+        super().__init__(device)
+        cfg = self.cfg = config_dict(config, _CONFIG_DEFAULTS, _CONFIG_INTS)
         if cfg["is_decoder"]:
             raise L.AedError("T5EncoderEngine: is_decoder=True -- only the encoder stack is implemented")
         self.gated, self.act = _activation(cfg["feed_forward_proj"])
@@ -114,21 +77,10 @@ class T5EncoderEngine:
         self.inner, self.dff, self.n_layers = self.H * self.D, cfg["d_ff"], cfg["num_layers"]
         self.eps = float(cfg["layer_norm_epsilon"])
         self._pack(state_dict)
-        self.stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
-        self._plans = collections.OrderedDict()
 
     # ------------------------------------------------------------------ weights
     def _pack(self, sd):
-        def get(*names):
-            for n in names:
-                if n in sd:
-                    return sd[n].detach().to(torch.float32)
-            raise L.AedError(f"T5EncoderEngine: the state dict has no '{names[0]}'")
-
-        def put(t, shape):
-            if tuple(t.shape) != tuple(shape):
-                raise L.AedError(f"T5EncoderEngine: a weight has shape {tuple(t.shape)}, the config says {tuple(shape)}")
-            return t.contiguous().to(self.device)
+        get, put = lambda *names: self._get(sd, *names), self._put      # noqa: E731
         dm, inner, dff = self.dm, self.inner, self.dff
         w = self.w = {"shared": put(get("shared.weight", "encoder.embed_tokens.weight"), (self.vocab, dm))}
         for i in range(self.n_layers):
@@ -151,11 +103,6 @@ class T5EncoderEngine:
         if tuple(self.rel_bias.shape) != (self.cfg["relative_attention_num_buckets"], self.H):
             raise L.AedError(f"T5EncoderEngine: relative_attention_bias has shape {tuple(self.rel_bias.shape)}, the config says "
                              f"{(self.cfg['relative_attention_num_buckets'], self.H)}")
-
-    @property
-    def weight_bytes(self):
-        """Device memory of the packed weights."""
-        return sum(t.numel() * t.element_size() for t in self.w.values())
 
     def position_bias(self, L_):
         """float[H, 2L - 1] on the host: pos[h][delta + L - 1] = relative_attention_bias[bucket(delta), h]."""
@@ -213,18 +160,6 @@ class T5EncoderEngine:
         tp.rmsnorm(h, w["final_ln"], out, rows=M, width=dm, eps=self.eps, name="final_ln")
         return dict(tape=tp, ids=ids, mask=mask, out=out.view(B, L_, dm), B=B, L=L_, graph=False)
 
-    def _plan(self, B, L_):
-        key = (B, L_, getattr(tape_mod._regime, "arith", None) or tape_mod.DEFAULT_ARITH)
-        plan = self._plans.pop(key, None)
-        if plan is None:
-            while len(self._plans) >= self.MAX_SHAPES:
-                if self.stream is not None:
-                    torch.cuda.synchronize(self.device)         # an evicted plan's graph may still be in flight
-                self._plans.popitem(last=False)                 # (its Tape destroys the graph)
-            plan = self.build_plan(B, L_)
-        self._plans[key] = plan                                 # most recently used last
-        return plan
-
     # ------------------------------------------------------------------ run
     def check_inputs(self, input_ids, attention_mask=None):
         """Host-side refusals; returns (ids int32 [B, L], mask int32 [B, L]) on the host."""
@@ -251,58 +186,22 @@ class T5EncoderEngine:
     @torch.inference_mode()
     def encode(self, input_ids, attention_mask=None, use_graph=True):
         ids, mask = self.check_inputs(input_ids, attention_mask)
-        if self.device.type != "cuda":
-            raise L.AedError(f"T5EncoderEngine on device={self.device} builds tapes only; running needs an MI355X (HIP) -- "
-                             f"there is no CPU fallback")
-        B, L_ = ids.shape
+        self._require_gpu()
+
+        def fill(plan):
+            plan["ids"].copy_(ids.reshape(-1))
+            plan["mask"].copy_(mask.reshape(-1))
         with torch.cuda.device(self.device):
-            plan = self._plan(B, L_)
-            tp = plan["tape"]
-            cur = torch.cuda.current_stream(self.device)
-            self.stream.wait_stream(cur)
-            with torch.cuda.stream(self.stream):
-                plan["ids"].copy_(ids.reshape(-1))
-                plan["mask"].copy_(mask.reshape(-1))
-                if not use_graph:
-                    tp.run()
-                else:
-                    if not plan["graph"]:
-                        tp.run()                                # once outside capture: a refused record raises here
-                        tp.capture()
-                        plan["graph"] = True
-                    tp.replay()
-            cur.wait_stream(self.stream)
+            plan = self._plan(*ids.shape)
+            self._run(plan, fill, use_graph)
             return plan["out"].clone()
 
 
-class NativeT5Encoder:
+class NativeT5Encoder(NativeTextModule):
     """Drop-in for the `transformers.T5EncoderModel` slot of `text_encoders.TextEncoders`: called with
     (input_ids, attention_mask) it returns a one-element tuple of the last hidden state, computed by a T5EncoderEngine."""
 
-    def __init__(self, engine, config=None):
-        self.engine = engine
-        if config is None or isinstance(config, dict):
-            config = SimpleNamespace(**{"model_type": "t5", **(config or engine.cfg)})
-        self.config = config
-
-    @classmethod
-    def from_module(cls, hf_module, device):
-        """From a live transformers T5EncoderModel (its state dict is copied; the module itself is not kept)."""
-        return cls(T5EncoderEngine(hf_module.config, hf_module.state_dict(), device), hf_module.config)
-
-    @classmethod
-    def from_pretrained(cls, path, device):
-        """From a checkpoint directory (config.json + model.safetensors | sharded safetensors | pytorch_model.bin) without
-        building a torch module."""
-        cfg, sd = read_checkpoint(path)
-        cfg.setdefault("model_type", "t5")
-        return cls(T5EncoderEngine(cfg, sd, device), SimpleNamespace(**cfg))
-
-    def parameters(self):
-        return iter(self.engine.w.values())
-
-    def eval(self):
-        return self
+    ENGINE, MODEL_TYPE = T5EncoderEngine, "t5"
 
     def __call__(self, input_ids=None, attention_mask=None, **_ignored):
         if input_ids is None:

@@ -199,6 +199,29 @@ def test_causal_attention(arith, D, H):
                 assert torch.equal(got[2, only0].cpu(), v[2, 0].expand(len(only0), -1))
 
 
+@pytest.mark.parametrize("D", [16, 64])
+def test_causal_last_row_is_the_t5_row_with_zero_bias(D):
+    """The causal and the T5 attention are one tile body (csrc/text_attn_tile.h) under two policies.  For these head sizes
+    1/sqrt(D) is a power of two, so scaling q by it commutes with every fmaf and add of the dot product, and adding a zero bias
+    changes no value: the single causal row Nq = 1, q0 = L - 1 equals row L - 1 of the T5 attention over the same k, v and key
+    mask with q / sqrt(D) and an all-zero pos table, bit for bit.  L = one key tile short, full, one over, and three tiles."""
+    B, H = 3, 3
+    inner, scale = H * D, 1.0 / D ** 0.5
+    for Ls in (5, 64, 65, 130):
+        g = torch.Generator().manual_seed(100 * D + Ls)
+        q, k, v = (torch.randn(B, Ls, inner, generator=g).to(DEV) * 1.5 for _ in range(3))
+        mask = attn_masks(B, Ls).to(DEV)
+        causal, full = guarded(B, 1, inner), guarded(B * Ls, inner)
+        tp = Tape(DEV)
+        tp.causal_attention(q[:, Ls - 1:, :], k, v, mask, causal, B=B, H=H, Nq=1, q0=Ls - 1, D=D, ldq=inner, ldk=inner, ldv=inner,
+                            ldo=inner, bsq=Ls * inner, bsk=Ls * inner, bsv=Ls * inner, bso=inner, bsm=Ls)
+        tp.t5_attention((q * scale).view(B * Ls, inner), k.view(B * Ls, inner), v.view(B * Ls, inner),
+                        torch.zeros(H, 2 * Ls - 1, device=DEV), mask, full, B=B, H=H, N=Ls, D=D, ldq=inner, ldk=inner, ldv=inner,
+                        ldo=inner)
+        run(tp)
+        assert torch.isfinite(causal).all() and torch.equal(causal[:, 0], full.view(B, Ls, inner)[:, Ls - 1]), (D, Ls)
+
+
 # ---------------------------------------------------------------------------------------- the engine against the fixture
 _CACHE = {}
 
