@@ -22,6 +22,8 @@ struct CGParams {
                              // of g row panels, m fastest inside a group -- the workgroups that run together on an XCD then cover
                              // g A panels x (resident / g) W tiles instead of ~1 panel x ALL W tiles (wide Linears: W larger
                              // than the 4 MB L2 was re-streamed for every row panel; profiles/r06_tile_order.md)
+    int loader;              // conv_gemm_x6 only (its launcher sets it): how the loader addresses its rows, x6_loader_addr.h --
+                             // 0 = reference form, 1 = affine offsets + tap masks, 2 = Linear (k in the scalar offset)
     int M, N, K;
     int lda, ldc, ldr, ld_rv;
     int IH, IW, OH, OW, Cin;

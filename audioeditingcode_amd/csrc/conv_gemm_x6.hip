@@ -17,7 +17,14 @@
 //
 // Data path: operands stay fp32 in HBM (no second copy of weights or activations).  Loads are buffer loads: a lane whose
 // element does not exist (conv zero padding, rows past M / N, a chunk past the block's k range) gets offset X6_OOB and
-// the hardware returns 0 -- no masks or selects on the data.  The loader threads split each float4 into three packed-bf16
+// the hardware returns 0 -- no masks or selects on the data.  Where a row reads is x6_loader_addr.h, in one of three forms the
+// launcher picks per record (CGParams::loader; the kernel tests it once, outside the K loop): Linear -- the vector offsets
+// never change and the chunk's k is the scalar offset of the loads; affine (no nearest upsampling, <= 31 taps) -- per A row
+// one add of the chunk's tap delta, one test of the row's tap mask, one select; reference (nearest upsampling, flag bit 18) --
+// position and bounds recomputed per row and chunk as in rounds 3-6 (also all that the wide-chunk kernels with an activation /
+// LayerNorm loader carry: x6_has_forms).  Same loads in the same order: the three forms give bit-identical outputs
+// (tools/x6_loader_addr_check.cpp on the host, tests/test_gpu_zz_x6_affine_loader.py on the GPU; profiles/x6_affine_loader.md).
+// The loader threads split each float4 into three packed-bf16
 // pieces (v_cvt_pk_bf16_f32 RNE + scalar subtractions: 5.5 VALU per element; v_pk_add_f32 issues badly beside MFMAs) while
 // writing the LDS stage.  LDS row = [hi 16 k | mid 16 k | lo 16 k | 16 B pad] = 112 B: the fragment read of one piece is
 // one ds_read_b128 per lane (8 consecutive k), conflict-free with this stride (28 dwords: the 16 rows of a b128 lane
@@ -34,6 +41,8 @@
 // AGPRs (4x slower as compiled), a row-permuted loader for conflict-free ds_write_b64 (-4 %), LDS-write / VMEM groups in
 // the hints (the solver gives up), packed subtractions (-10 %), flat loads with LDS-side zero masking (-3 %).
 #include "cg_params.h"
+#include "x6_loader_addr.h"
+#include <type_traits>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -64,7 +73,18 @@ __device__ __forceinline__ void x6_split_pair(float x0, float x1, unsigned& h, u
 }
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned X6_OOB = 0x80000000u;        // byte offset past every buffer (num_records 0x7ffffff0): the load returns 0
+
+// which instantiations carry the affine and Linear K loops next to the reference one (see the end of the kernel)
+constexpr bool x6_has_forms(bool plain, int bk) { return plain || bk == 16; }
+
+__host__ __device__ __forceinline__ X6Geo x6_geo(const CGParams& p) {
+    X6Geo g;
+    g.M = p.M; g.N = p.N; g.K = p.K; g.Cin = p.Cin; g.C1 = p.C1; g.KH = p.KH; g.KW = p.KW; g.IW = p.IW; g.vIH = p.vIH; g.vIW = p.vIW;
+    g.stride = p.stride; g.pad_h = p.pad_h; g.pad_w = p.pad_w; g.dil_h = p.dil_h; g.dil_w = p.dil_w; g.up = p.up; g.rpb = p.rpb;
+    g.OW = p.OW; g.kgroup = p.kgroup;
+    g.lda = (unsigned)p.lda; g.lda2 = (unsigned)p.lda2; g.a_bs = (unsigned)p.a_bs; g.a_bs2 = (unsigned)p.a_bs2;
+    return g;
+}
 
 // Compile-time interleave request for one chunk body: NM MFMAs with NV VALU instructions spread evenly between them
 // (sched_group_barrier wants immediates, hence the recursion).
@@ -137,50 +157,18 @@ __global__ __launch_bounds__(64 * WROWS * WCOLS, 2) void conv_gemm_x6_kernel(CGP
     const int lq = tid % TPR;               // which float4 of the 16-k row
     const int lcol = lq * 4;
 
-    int ay0[PA], ax0[PA];
-    unsigned abase[PA], abase2[PA];
-    bool avalid[PA];
+    // where the loader reads: x6_loader_addr.h (row origins here, the per-chunk part in k_loop below)
+    const X6Geo g = x6_geo(p);
+    X6Row arow[PA];
 #pragma unroll
-    for (int q = 0; q < PA; ++q) {
-        const int m = m0 + lrow + RPP * q;
-        avalid[q] = m < p.M;
-        const int mm = avalid[q] ? m : 0;
-        int b = 0, r = mm, oy = mm, ox = 0;
-        if (p.rpb != p.M || p.OW != 1) {        // (a Linear is one batch item of M x 1 pixels: no run-time divisions in its prologue)
-            b = mm / p.rpb;
-            r = mm - b * p.rpb;
-            oy = r / p.OW;
-            ox = r - oy * p.OW;
-        }
-        ay0[q] = oy * p.stride - p.pad_h;
-        ax0[q] = ox * p.stride - p.pad_w;
-        abase[q] = (unsigned)b * (unsigned)p.a_bs + lcol;
-        abase2[q] = (unsigned)b * (unsigned)p.a_bs2 + lcol;
-    }
+    for (int q = 0; q < PA; ++q) arow[q] = x6_row(g, m0 + lrow + RPP * q, lcol);
     unsigned wbase[PB];
     bool wvalid[PB];
 #pragma unroll
     for (int q = 0; q < PB; ++q) {
         const int n = n0 + lrow + RPP * q;
         wvalid[q] = n < p.N;
-        wbase[q] = (unsigned)(wvalid[q] ? n : 0) * (unsigned)p.K + lcol;
-    }
-    const int vIH = p.vIH, vIW = p.vIW;
-    // running (tap, channel) position of the next chunk to prefetch: prefetch() is called with consecutive kc
-    // [group of p.kgroup channels][tap][chunk within the group] (cg_params.h): pf_cg = first channel of the group
-    int pf_cg, pf_sub, pf_ty, pf_tx;
-    const int gq = p.kgroup / BK;             // chunks per (group, tap)
-    if (kc_begin == 0) {
-        pf_cg = pf_sub = pf_ty = pf_tx = 0;
-    } else {
-        const int per_group = p.KH * p.KW * gq;
-        const int g = kc_begin / per_group;
-        const int rem = kc_begin - g * per_group;
-        const int tap = rem / gq;
-        pf_cg = g * p.kgroup;
-        pf_sub = rem - tap * gq;
-        pf_ty = tap / p.KW;
-        pf_tx = tap - pf_ty * p.KW;
+        wbase[q] = x6_w_base(g, n, lcol);
     }
 
     float4 rbuf_a[DEPTH][PA], rbuf_b[DEPTH][PB];
@@ -191,43 +179,12 @@ __global__ __launch_bounds__(64 * WROWS * WCOLS, 2) void conv_gemm_x6_kernel(CGP
     // Buffer descriptors over "everything below 2 GB" (the launcher checks the operands fit): an offset of X6_OOB is out of
     // range and reads 0.  Branch-free on purpose: the whole chunk body (split of chunk k+1, loads of chunk k+1+DEPTH, MFMAs
     // of chunk k) is ONE basic block, so VALU / LDS / VMEM work can sit in the shadow of the MFMAs.
-    const __amdgpu_buffer_rsrc_t srd_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7ffffff0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t srd_a2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A2 ? p.A2 : p.A), 0, 0x7ffffff0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t srd_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0x7ffffff0, 0x00020000);
+    // (the A descriptor is made per chunk from the chunk's source pointer: the two sources differ in their base only)
+    const float* const a_src2 = p.A2 ? p.A2 : p.A;
+    auto srd_of = [](const float* ptr) { return __builtin_amdgcn_make_buffer_rsrc((void*)ptr, 0, X6_NUM_RECORDS, 0x00020000); };
+    const __amdgpu_buffer_rsrc_t srd_w = srd_of(p.W);
     auto as_f4 = [](u32x4 v) {
         return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-    };
-    auto prefetch = [&](int kc, float4 (&ra)[PA], float4 (&rb)[PB]) {
-        int c0 = pf_cg + pf_sub * BK;
-        const int dy = pf_ty * p.dil_h, dx = pf_tx * p.dil_w;
-        const unsigned k0 = (unsigned)((pf_ty * p.KW + pf_tx) * p.Cin + c0);     // W column of this chunk
-        pf_sub += 1;
-        const bool wrap = pf_sub == gq;
-        pf_sub = wrap ? 0 : pf_sub;
-        pf_tx += wrap ? 1 : 0;
-        const bool wrap2 = pf_tx == p.KW;
-        pf_tx = wrap2 ? 0 : pf_tx;
-        pf_ty += wrap2 ? 1 : 0;
-        const bool wrap3 = pf_ty == p.KH;
-        pf_ty = wrap3 ? 0 : pf_ty;
-        pf_cg += wrap3 ? p.kgroup : 0;
-        const bool second = p.C1 > 0 && c0 >= p.C1;         // two-source A: block-uniform select per chunk
-        c0 -= second ? p.C1 : 0;
-        const unsigned ld = second ? (unsigned)p.lda2 : (unsigned)p.lda;
-        // a chunk past this block's k range, an out-of-image tap, a row past M or N: the lane's offset is X6_OOB
-        const bool dead = kc >= kc_end;
-#pragma unroll
-        for (int q = 0; q < PA; ++q) {
-            const int iy = ay0[q] + dy, ix = ax0[q] + dx;
-            const bool ok = avalid[q] & ((unsigned)iy < (unsigned)vIH) & ((unsigned)ix < (unsigned)vIW) & !dead;
-            const unsigned base = second ? abase2[q] : abase[q];
-            const unsigned off = (base + (unsigned)((iy >> p.up) * p.IW + (ix >> p.up)) * ld + (unsigned)c0) * 4u;
-            ra[q] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(second ? srd_a2 : srd_a, ok ? off : X6_OOB, 0, 0));
-        }
-#pragma unroll
-        for (int q = 0; q < PB; ++q)
-            rb[q] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(
-                srd_w, (wvalid[q] & !dead) ? (wbase[q] + k0) * 4u : X6_OOB, 0, 0));
     };
 
     // one fetched float4 -> three 8-byte piece groups of its LDS row
@@ -260,6 +217,10 @@ __global__ __launch_bounds__(64 * WROWS * WCOLS, 2) void conv_gemm_x6_kernel(CGP
             float4 v = ra[q];
             if constexpr (!PLAIN) {
                 if (p.ln_mode) {
+                    // Four products, three adds, never fused: stage_write is inlined once ahead of the K loop and once inside
+                    // every copy of it, and left to itself the compiler contracts some of those copies into FMAs and not others
+                    // (which ones moved when the loop was cloned per loader form: 5e-9 relative on the LayerNorm-folded records).
+#pragma clang fp contract(off)
                     ln_s1[q] += (v.x + v.y) + (v.z + v.w);
                     ln_s2[q] += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
                 }
@@ -315,43 +276,131 @@ __global__ __launch_bounds__(64 * WROWS * WCOLS, 2) void conv_gemm_x6_kernel(CGP
                 for (int b = 0; b < TN; ++b)
                     acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[a][TA[t]], fb[b][TB[t]], acc[a][b], 0, 0, 0);
     };
-    auto hints = [&]() {
+    auto hints = [&](auto loader_c) {
         if constexpr (SCHED == 1) {
             // a wave hides ~5 single-issue instructions per 32-cycle MFMA: spread the split of the chunk being staged (5.5 VALU
             // per element + addresses) between the MFMAs.  VALU groups only: asking for LDS-write / load groups as well makes
             // the solver give up and emit all VALU first.
             constexpr int NM = TM * TN * NTERMS * KB;
-            x6_hints<0, NM, NM * (((PA + PB) * 22 + 40 + NM - 1) / NM)>();
+            // address VALU per chunk: the reference form ~40; affine: add + bit test + select per A row, one select per W row;
+            // Linear: two selects per A row, one per W row
+            constexpr int LD = decltype(loader_c)::value;
+            constexpr int ADDR = LD == 0 ? 40 : LD == 1 ? 4 * PA + PB + 4 : 2 * PA + PB + 2;
+            x6_hints<0, NM, NM * (((PA + PB) * 22 + ADDR + NM - 1) / NM)>();
         }
     };
 
+    // The K loop, once per loader form (p.loader, chosen by the launcher: block-uniform, tested once outside the loop).
+    //   0  reference: position and bounds recomputed per chunk (nearest-upsample records, > 31 taps, op flag bit 18)
+    //   1  affine: per A row one add, one bit test of its tap mask and one select; W rows keep their vector offset and take
+    //      the chunk's column as the scalar offset
+    //   2  Linear: the vector offsets never change; the only running value is the byte k in the scalar offsets
+    auto k_loop = [&](auto loader_c) __attribute__((always_inline)) {
+        constexpr int LD = decltype(loader_c)::value;
+        X6Pos pos = {0, 0, 0, 0};
+        X6Walk walk = {0, 0, 0};
+        unsigned tap_pixb = 0, tap_kb = 0;      // lane t: the two per-tap values of tap t
+        X6RowAff raff[PA];
+        unsigned av[PA], av2[PA], wv[PB];
+        unsigned kb = 0;
+        if constexpr (LD == 0) {
+            pos = x6_pos_at(g, kc_begin, BK);
+        } else {
 #pragma unroll
-    for (int d = 0; d < DEPTH; ++d) prefetch(kc_begin + d, rbuf_a[d], rbuf_b[d]);
-    stage_write(lds, rbuf_a[0], rbuf_b[0]);
-    prefetch(kc_begin + DEPTH, rbuf_a[0], rbuf_b[0]);
-    __syncthreads();
-    int cur = 0;
-    // The trip count is rounded up to a multiple of DEPTH (static register slots, no exit inside the unrolled body): a chunk
-    // past kc_end was loaded as zeros and its MFMAs add nothing.  Per iteration, in program order: fragment reads of chunk kc
-    // (stage cur) -> split + LDS write of chunk kc+1 (other stage) -> loads of chunk kc+1+DEPTH -> MFMAs of chunk kc -> barrier.
-    for (int kc0 = kc_begin; kc0 < kc_end; kc0 += DEPTH) {
-#pragma unroll
-        for (int d = 0; d < DEPTH; ++d) {
-            const int kc = kc0 + d;
-            const int sl = (d + 1) % DEPTH;     // chunk kc+1 sits in this register slot
-            load_frags(lds + cur * STAGE, 0, af, bw);
-            stage_write(lds + (cur ^ 1) * STAGE, rbuf_a[sl], rbuf_b[sl]);
-            prefetch(kc + 1 + DEPTH, rbuf_a[sl], rbuf_b[sl]);
-            do_mfmas(af, bw);
-            if constexpr (KB == 2) {            // second k-block of the wide chunk: fragments read under the first block's MFMAs
-                bf16x8 af2[TM][3], bw2[TN][3];
-                load_frags(lds + cur * STAGE, 1, af2, bw2);
-                do_mfmas(af2, bw2);
+            for (int q = 0; q < PA; ++q) {
+                raff[q] = x6_row_affine(g, arow[q]);
+                av[q] = x6_lin_voff(raff[q].off, raff[q].mask);
+                av2[q] = x6_lin_voff(raff[q].off2, raff[q].mask);
             }
-            hints();
-            __syncthreads();
-            cur ^= 1;
+#pragma unroll
+            for (int q = 0; q < PB; ++q) wv[q] = x6_w_voff(wbase[q], wvalid[q]);
+            if constexpr (LD == 1) {
+                walk = x6_walk_at(g, kc_begin, BK);
+                const int t = lane < p.KH * p.KW ? lane : 0;
+                tap_pixb = x6_tap_pixb(g, t);
+                tap_kb = x6_tap_kb(g, t);
+            } else {
+                kb = (unsigned)kc_begin * (BK * 4u);
+            }
         }
+        // prefetch() is called with consecutive kc.  A chunk past this block's k range, an out-of-image tap, a row past M or
+        // N: the lane's vector offset is X6_OOB
+        auto prefetch = [&](int kc, float4 (&ra)[PA], float4 (&rb)[PB]) {
+            const bool dead = kc >= kc_end;
+            if constexpr (LD == 0) {
+                const X6Chunk c = x6_pos_step(g, pos, BK);
+                const __amdgpu_buffer_rsrc_t srd_a = srd_of(c.second ? a_src2 : p.A);
+#pragma unroll
+                for (int q = 0; q < PA; ++q)
+                    ra[q] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(srd_a, x6_a_off(g, arow[q], c, dead), 0, 0));
+#pragma unroll
+                for (int q = 0; q < PB; ++q)
+                    rb[q] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(srd_w, x6_w_off(wbase[q], wvalid[q], c.k0, dead), 0, 0));
+            } else if constexpr (LD == 1) {
+                const unsigned pixb = __builtin_amdgcn_readlane(tap_pixb, walk.tap), tapkb = __builtin_amdgcn_readlane(tap_kb, walk.tap);
+                const X6ChunkAff c = x6_walk_step(g, walk, BK, dead, pixb, tapkb);
+                const __amdgpu_buffer_rsrc_t srd_a = srd_of(c.second ? a_src2 : p.A);
+#pragma unroll
+                for (int q = 0; q < PA; ++q) {
+                    // the add is done whether the tap is live or not (left alone, the compiler sinks it and the chunk's uniform
+                    // arithmetic into a divergent branch per row: the chunk body would no longer be one basic block)
+                    unsigned sum = x6_a_sum_affine(raff[q], c);
+                    asm volatile("" : "+v"(sum));
+                    ra[q] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(srd_a, x6_a_sel_affine(raff[q], c, sum), 0, 0));
+                }
+#pragma unroll
+                for (int q = 0; q < PB; ++q)
+                    rb[q] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(srd_w, x6_dead_voff(wv[q], dead), (int)c.k0b, 0));
+            } else {
+                // (the second source's -4 * C1 sits in its base address, so kb is the scalar offset of either source)
+                const X6ChunkLin c = x6_linear_chunk(g, kb);
+                const __amdgpu_buffer_rsrc_t srd_a = srd_of(c.second ? a_src2 - p.C1 : p.A);
+#pragma unroll
+                for (int q = 0; q < PA; ++q)
+                    ra[q] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(srd_a, x6_dead_voff(c.second ? av2[q] : av[q], dead), (int)kb, 0));
+#pragma unroll
+                for (int q = 0; q < PB; ++q)
+                    rb[q] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(srd_w, x6_dead_voff(wv[q], dead), (int)kb, 0));
+                kb += BK * 4u;
+            }
+        };
+#pragma unroll
+        for (int d = 0; d < DEPTH; ++d) prefetch(kc_begin + d, rbuf_a[d], rbuf_b[d]);
+        stage_write(lds, rbuf_a[0], rbuf_b[0]);
+        prefetch(kc_begin + DEPTH, rbuf_a[0], rbuf_b[0]);
+        __syncthreads();
+        int cur = 0;
+        // The trip count is rounded up to a multiple of DEPTH (static register slots, no exit inside the unrolled body): a chunk
+        // past kc_end was loaded as zeros and its MFMAs add nothing.  Per iteration, in program order: fragment reads of chunk kc
+        // (stage cur) -> split + LDS write of chunk kc+1 (other stage) -> loads of chunk kc+1+DEPTH -> MFMAs of chunk kc -> barrier.
+        for (int kc0 = kc_begin; kc0 < kc_end; kc0 += DEPTH) {
+#pragma unroll
+            for (int d = 0; d < DEPTH; ++d) {
+                const int kc = kc0 + d;
+                const int sl = (d + 1) % DEPTH;     // chunk kc+1 sits in this register slot
+                load_frags(lds + cur * STAGE, 0, af, bw);
+                stage_write(lds + (cur ^ 1) * STAGE, rbuf_a[sl], rbuf_b[sl]);
+                prefetch(kc + 1 + DEPTH, rbuf_a[sl], rbuf_b[sl]);
+                do_mfmas(af, bw);
+                if constexpr (KB == 2) {            // second k-block of the wide chunk: fragments read under the first block's MFMAs
+                    bf16x8 af2[TM][3], bw2[TN][3];
+                    load_frags(lds + cur * STAGE, 1, af2, bw2);
+                    do_mfmas(af2, bw2);
+                }
+                hints(loader_c);
+                __syncthreads();
+                cur ^= 1;
+            }
+        }
+    };
+    // The wide-chunk kernels with an activation / LayerNorm loader sit at the register limit with one loop (217 of 256 VGPRs on
+    // the 256x128 tile): three loops in one allocation made that tile spill inside its K loop, so they keep the reference form.
+    if constexpr (x6_has_forms(PLAIN, BK)) {
+        if (p.loader == 2) k_loop(std::integral_constant<int, 2>{});
+        else if (p.loader == 1) k_loop(std::integral_constant<int, 1>{});
+        else k_loop(std::integral_constant<int, 0>{});
+    } else {
+        k_loop(std::integral_constant<int, 0>{});
     }
 
     float* ln_stat = reinterpret_cast<float*>(lds);      // [BM][2] (mean, rstd); the operand stages are dead
@@ -382,6 +431,7 @@ static int x6_launch(const CGParams& p, bool plain, int sched, int terms, hipStr
 // per-batch weights / grouped softmax) run the fp32 path.
 // Flag bit 3 (8): WITHOUT it the compiler orders the chunk body itself (A/B switch; tapes set it).
 // Flag bit 4 (16): DIAGNOSTIC three-term arithmetic (~4e-6 rel error; tells how much of the kernel time is matrix-pipe time).
+// Flag bit 18 (0x40000): keep the reference loader (A/B of the affine / Linear loader; tapes do not set it).
 int launch_conv_gemm_x6(const aed_op* op, hipStream_t s) {
     const int32_t* i = op->i;
     const int Cin = i[11];
@@ -435,7 +485,13 @@ int launch_conv_gemm_x6(const aed_op* op, hipStream_t s) {
             if (op->flags & 0x3800) p.gm = 1 << ((op->flags >> 11) & 7);       // flag bits 11-13: forced group height (sweeps)
         }
     }
+    // loader form (x6_loader_addr.h): Linear > affine > reference; flag bit 18 (0x40000) keeps the reference form (A/B)
+    {
+        const X6Geo g = x6_geo(p);
+        p.loader = (op->flags & 0x40000) ? 0 : x6_linear_ok(g) ? 2 : x6_affine_ok(g) ? 1 : 0;
+    }
     const bool plain = p.in_act == 0 && p.ln_mode == 0;
+    if (!x6_has_forms(plain, wide ? 32 : X6_BK)) p.loader = 0;
     const int sched = (op->flags & 8) ? 1 : 0;
     const int terms = (op->flags & 16) ? 3 : 6;
     if (p.geglu) AED_REQUIRE(cfg == 1 || cfg == 3 || cfg == 8 || cfg == 9, "conv_gemm_x6: the GEGLU epilogue needs 64-wide wave tiles (cfg %d)", cfg);

@@ -54,6 +54,9 @@ enum aed_opcode {
                                  group height 2^v (sweeps); bit 15 (0x8000): always the general epilogue (A/B of the simple-rows epilogue);
                                  bits 16-17: the stream this record runs on is masked to (all CUs) >> v compute units (sizes the
                                  tile groups; tapes built under tape.tile_regime set it);
+                                 bit 18 (0x40000): with bit 2, keep the reference loader -- position and bounds recomputed per row
+                                 and chunk -- instead of affine row offsets with tap masks (A/B; tapes do not set it; nearest-
+                                 upsample records always take the reference loader; csrc/x6_loader_addr.h);
                                  bit 6 (EXPERIMENT, tapes built under tape.arith_mode("fp8")): contract on the MX-FP8 matrix
                                  cores (csrc/conv_gemm_f8.hip: OCP microscaling e4m3, one e8m0 scale per 32 k of a row,
                                  quantised in the loader, v_mfma_scale_f32_32x32x64_f8f6f4, fp32 accumulate).  NOT a parity

@@ -62,9 +62,10 @@ def classify(op):
     return None
 
 
-def census(body):
-    """Counts of the loop with the most MFMAs, plus a histogram of its vector opcodes."""
-    labels, best = {}, None
+def census(body, every=False):
+    """Counts of the loop with the most MFMAs, plus a histogram of its vector opcodes (every: the list of all MFMA loops in
+    program order, each with its scalar histogram as a third element)."""
+    labels, best, loops = {}, None, []
     for n, ln in enumerate(body):
         m = LABEL.match(ln)
         if m:
@@ -72,7 +73,7 @@ def census(body):
             continue
         m = BRANCH.match(ln)
         if m and m.group(1) in labels:                                   # a back edge: the loop is body[label .. here]
-            cnt, hist = dict.fromkeys(("mfma", "trans", "packed", "vector", "lds", "mem", "scalar"), 0), {}
+            cnt, hist, shist = dict.fromkeys(("mfma", "trans", "packed", "vector", "lds", "mem", "scalar"), 0), {}, {}
             for l2 in body[labels[m.group(1)]:n + 1]:
                 mi = INSN.match(l2)
                 kind = classify(mi.group(1)) if mi else None
@@ -80,9 +81,13 @@ def census(body):
                     cnt[kind] += 1
                     if kind in ("trans", "packed", "vector"):
                         hist[mi.group(1)] = hist.get(mi.group(1), 0) + 1
+                    if kind == "scalar":
+                        shist[mi.group(1)] = shist.get(mi.group(1), 0) + 1
+            if cnt["mfma"]:
+                loops.append((cnt, hist, shist))
             if best is None or cnt["mfma"] > best[0]["mfma"]:
                 best = (cnt, hist)
-    return best
+    return loops if every else best
 
 
 def demangle(names):
@@ -102,6 +107,8 @@ def main():
     ap.add_argument("--kernel", default="", help="only kernels whose (demangled) name contains this")
     ap.add_argument("--arch", default=os.environ.get("AED_ARCH", "gfx950"))
     ap.add_argument("--top", type=int, default=0, help="also list the N most frequent vector opcodes of each loop")
+    ap.add_argument("--all-loops", action="store_true",
+                    help="one row per MFMA loop of a kernel, in program order (a kernel that picks one of several K loops per launch)")
     a = ap.parse_args()
     if a.path.endswith(".s"):
         text = open(a.path).read()
@@ -122,13 +129,19 @@ def main():
         if best is None or best[0]["mfma"] == 0:
             print(f"| `{names[name]}` | no MFMA loop | | | | | | | | |")
             continue
-        c, hist = best
-        nv = c["trans"] + c["packed"] + c["vector"]
-        print(f"| `{names[name]}` | {c['mfma']} | {c['trans']} | {c['packed']} | {c['vector']} | {nv} | {nv / c['mfma']:.1f} | "
-              f"{c['lds']} | {c['mem']} | {c['scalar']} |")
-        if a.top:
-            top = sorted(hist.items(), key=lambda kv: -kv[1])[:a.top]
-            print("|  | " + ", ".join(f"{k} {v}" for k, v in top) + " | | | | | | | | |")
+        rows = [(names[name], best[0], best[1], None)]
+        if a.all_loops:
+            rows = [(f"{names[name]} loop {n}", *lp) for n, lp in enumerate(census(body, every=True))]
+        for label, c, hist, shist in rows:
+            nv = c["trans"] + c["packed"] + c["vector"]
+            print(f"| `{label}` | {c['mfma']} | {c['trans']} | {c['packed']} | {c['vector']} | {nv} | {nv / c['mfma']:.1f} | "
+                  f"{c['lds']} | {c['mem']} | {c['scalar']} |")
+            if a.top:
+                top = sorted(hist.items(), key=lambda kv: -kv[1])[:a.top]
+                print("|  | " + ", ".join(f"{k} {v}" for k, v in top) + " | | | | | | | | |")
+                if shist:
+                    top = sorted(shist.items(), key=lambda kv: -kv[1])[:a.top]
+                    print("|  | " + ", ".join(f"{k} {v}" for k, v in top) + " | | | | | | | | |")
     return 0
 
 

@@ -8,8 +8,8 @@
 //   audioeditingcode_amd/x6_bench 1 cases           -> only the feature matrix (rc 1 if a case fails)
 //   audioeditingcode_amd/x6_bench 4 replay <records> [cus=N] [x6only]   -> every GEMM record of a forward, both arithmetics
 //   audioeditingcode_amd/x6_bench 4 replay <records> [cus=N] order [gm=v] -> tile-order A/B of the split-bf16 records (round 6)
-//   audioeditingcode_amd/x6_bench 4 replay <records> [cus=N] ab=A:B       -> A/B of two flag sets (e.g. 16384:0 = one tile per
-//                                                      workgroup vs the persistent walk), outputs compared bit for bit
+//   audioeditingcode_amd/x6_bench 4 replay <records> [cus=N] ab=A:B       -> A/B of two flag sets (e.g. 262144:0 = the reference
+//                                                      loader vs the affine one), outputs compared bit for bit
 //   audioeditingcode_amd/x6_bench 60 sweep <records> [cus=N] [x6] > sweep.json   -> tile sweep (tools/tile_sweep.py without
 //                                                      Python; the JSON feeds tools/tile_table_from_sweep.py)
 //   (records: PYTHONPATH=. python tools/dump_gemm_ops.py <unet batch> > file)
