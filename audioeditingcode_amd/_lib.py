@@ -41,6 +41,11 @@ T5_ATTN_MAX_L = 512                     # its longest sequence
 OP_LAYERNORM_ROWS, OP_ADD_ROWS, OP_GELU_NEW, OP_CAUSAL_ATTENTION = 41, 42, 43, 44
 LM_ATTN_HEAD_SIZES = (8, 16, 32, 64)    # head sizes AED_OP_CAUSAL_ATTENTION takes
 LM_ATTN_MAX_NK = 1024                   # its longest key/value cache
+# the CLAP text tower's ops beside the GEMMs and OP_LAYERNORM_ROWS (csrc/clap.hip); tape.embed_ln / gelu_erf /
+# encoder_attention name their records.  45 is unassigned (refused as a bad opcode)
+OP_EMBED_LN, OP_GELU_ERF, OP_ENCODER_ATTENTION = 46, 47, 48
+ENC_ATTN_HEAD_SIZES = (8, 16, 32, 64)   # head sizes AED_OP_ENCODER_ATTENTION takes
+ENC_ATTN_MAX_L = 512                    # its longest sequence
 SEG_MAX_P = 8               # prompts per row AED_OP_REVERSE_STEP_SEGMENTS takes
 PC_TAB_STRIDE = 4           # floats per slot of the ops' table: sqrt(abar_t), c0, c1, sigma_t^2 / const
 PC_MAX_EV = 8               # directions AED_OP_PC_ORTHONORMALISE takes

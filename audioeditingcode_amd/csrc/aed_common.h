@@ -68,6 +68,9 @@ int launch_layernorm_rows(const aed_op* op, hipStream_t s);
 int launch_add_rows(const aed_op* op, hipStream_t s);
 int launch_gelu_new(const aed_op* op, hipStream_t s);
 int launch_causal_attention(const aed_op* op, hipStream_t s);
+int launch_embed_ln(const aed_op* op, hipStream_t s);
+int launch_gelu_erf(const aed_op* op, hipStream_t s);
+int launch_encoder_attention(const aed_op* op, hipStream_t s);
 
 int aed_num_cus();
 

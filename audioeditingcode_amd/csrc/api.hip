@@ -64,6 +64,8 @@ static launcher_t g_table[AED_OP_COUNT] = {
     launch_t5_embed, launch_rmsnorm, launch_t5_attention, launch_gated_act,
     nullptr,              // 40 is unassigned (refused as a bad opcode)
     launch_layernorm_rows, launch_add_rows, launch_gelu_new, launch_causal_attention,
+    nullptr,              // 45 is unassigned (refused as a bad opcode)
+    launch_embed_ln, launch_gelu_erf, launch_encoder_attention,
 };
 
 extern "C" {

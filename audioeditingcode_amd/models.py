@@ -95,7 +95,7 @@ class PipelineWrapper(torch.nn.Module):
     def __init__(self, model_id: str, device: torch.device, double_precision: bool = False,
                  token: Optional[str] = None, seed: int = 0, state_dicts: Optional[Dict] = None,
                  allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None, text_lm: Optional[str] = None,
-                 *args, **kwargs) -> None:
+                 text_clap: Optional[str] = None, *args, **kwargs) -> None:
         super().__init__()
         self._init_common(model_id, device, double_precision, token, allow_synthetic)
         self.family = configs.get_family(model_id)
@@ -114,11 +114,11 @@ class PipelineWrapper(torch.nn.Module):
             self.weights_source = ckpt
             try:
                 from .text_encoders import TextEncoders
-                text_lm = resolve_text_lm(text_lm)
+                text_lm, text_clap = resolve_text_lm(text_lm), resolve_text_clap(text_clap)
                 self.text_encoders = TextEncoders.from_pretrained(ckpt, self.kind, device=self.device, t5=text_t5 or "torch",
-                                                                  lm=text_lm)
+                                                                  lm=text_lm, clap=text_clap)
                 self.conditioning_source = f"transformers text encoders from {ckpt}" + self._t5_note(text_t5) + \
-                    self._lm_note(text_lm)
+                    self._lm_note(text_lm) + self._clap_note(text_clap)
             except (FileNotFoundError, OSError, ImportError) as e:
                 if not self.synthetic_ok:
                     raise L.AedError(f"{ckpt}: U-Net/VAE/vocoder weights were found but the text-conditioning "
@@ -180,6 +180,13 @@ class PipelineWrapper(torch.nn.Module):
             return ""
         return " (GPT-2 language model: native op tape)" if self.kind == "audioldm2" else \
             " (no language model in this family: text_lm has no effect)"
+
+    def _clap_note(self, text_clap) -> str:
+        """What `conditioning_source` says about the CLAP text tower when the native one was asked for."""
+        if text_clap != "native":
+            return ""
+        return " (CLAP text tower: native op tape)" if self.kind in ("audioldm", "audioldm2") else \
+            " (no CLAP in this family: text_clap has no effect)"
 
     def _require_device(self) -> None:
         """The product runs on HIP only.  (The CPU test suite subclasses the wrapper and overrides this hook to execute
@@ -564,7 +571,7 @@ class StableAudWrapper(PipelineWrapper):
     def __init__(self, model_id: str, device: torch.device, double_precision: bool = False,
                  token: Optional[str] = None, seed: int = 0, state_dicts: Optional[Dict] = None,
                  allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None, text_lm: Optional[str] = None,
-                 *args, **kwargs) -> None:
+                 text_clap: Optional[str] = None, *args, **kwargs) -> None:
         torch.nn.Module.__init__(self)
         self._init_common(model_id, device, double_precision, token, allow_synthetic)
         self.family = configs.get_family(model_id)
@@ -587,7 +594,7 @@ class StableAudWrapper(PipelineWrapper):
                 self.text_encoders = TextEncoders.from_pretrained(ckpt, "stable_audio", device=self.device,
                                                                   t5=text_t5 or "torch")
                 self.conditioning_source = f"transformers text encoder from {ckpt}" + self._t5_note(text_t5) + \
-                    self._lm_note(resolve_text_lm(text_lm))
+                    self._lm_note(resolve_text_lm(text_lm)) + self._clap_note(resolve_text_clap(text_clap))
             except (FileNotFoundError, OSError, ImportError) as e:
                 if not self.synthetic_ok:
                     raise L.AedError(f"{ckpt}: DiT/VAE weights were found but the text-conditioning components could "
@@ -842,25 +849,39 @@ def resolve_text_lm(text_lm: Optional[str]) -> str:
     return text_lm
 
 
+def resolve_text_clap(text_clap: Optional[str]) -> str:
+    """"torch" or "native": the argument, or the environment variable AED_TEXT_CLAP when the argument is None."""
+    if text_clap is None:
+        text_clap = os.environ.get("AED_TEXT_CLAP") or "torch"
+    if text_clap not in ("torch", "native"):
+        raise ValueError(f"text_clap={text_clap!r}: expected 'torch' or 'native'")
+    return text_clap
+
+
 def load_model(model_id: str, device: torch.device, num_diffusion_steps: int, double_precision: bool = False,
                token: Optional[str] = None, seed: int = 0, state_dicts: Optional[Dict] = None,
                allow_synthetic: Optional[bool] = None, text_t5: Optional[str] = None,
-               text_lm: Optional[str] = None) -> PipelineWrapper:
+               text_lm: Optional[str] = None, text_clap: Optional[str] = None) -> PipelineWrapper:
     """Substring dispatch + scheduler setup of models.py:1357-1374.  `allow_synthetic`: opt-in to seeded-random weights
     and stand-in text embeddings when no checkpoint is on disk (benchmarks / tests; see PipelineWrapper.__init__).
     `text_t5`: "torch" (default) or "native" -- which T5 encoder `TextEncoders.from_pretrained` loads for the families that
     have one (TANGO, Stable Audio, AudioLDM2's second encoder); no effect on stand-in conditioning.
     `text_lm`: "torch" (default) or "native" -- whether AudioLDM2's GPT-2 prompt states come from `transformers.GPT2Model` or
     from `lm.NativeGPT2` (one tape per prompt-batch shape); None reads the environment variable AED_TEXT_LM; no effect on
-    other families or on stand-in conditioning."""
+    other families or on stand-in conditioning.
+    `text_clap`: "torch" (default) or "native" -- whether the CLAP text embedding of AudioLDM and AudioLDM2 comes from the
+    transformers module or from `clap.NativeClapText` / `clap.NativeClapModel` (one tape per prompt-batch shape, padded columns
+    trimmed); None reads the environment variable AED_TEXT_CLAP; no effect on TANGO, Stable Audio or stand-in conditioning."""
     if text_t5 not in (None, "torch", "native"):
         raise ValueError(f"text_t5={text_t5!r}: expected 'torch' or 'native'")
     text_lm = resolve_text_lm(text_lm)
+    text_clap = resolve_text_clap(text_clap)
     fam = configs.family_of(model_id)
     cls = {"tango": TangoWrapper, "audioldm2": AudioLDM2Wrapper, "audioldm": AudioLDMWrapper,
            "stable_audio": StableAudWrapper}[fam]
     ldm_stable = cls(model_id=model_id, device=device, double_precision=double_precision, token=token, seed=seed,
-                     state_dicts=state_dicts, allow_synthetic=allow_synthetic, text_t5=text_t5, text_lm=text_lm)
+                     state_dicts=state_dicts, allow_synthetic=allow_synthetic, text_t5=text_t5, text_lm=text_lm,
+                     text_clap=text_clap)
     ldm_stable.load_scheduler()
     ldm_stable.model.scheduler.set_timesteps(num_diffusion_steps, device=None)
     torch.cuda.empty_cache()

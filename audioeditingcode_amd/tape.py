@@ -687,6 +687,31 @@ class Tape:
                   nbytes=4 * B * H * D * (2 * Nq + 2 * Nk))
         return out
 
+    # ------------------------------------------------------------------ CLAP text tower ops (csrc/clap.hip)
+    def embed_ln(self, ids, pos_ids, word, pos, type_row, g, b, out, *, rows, width, eps, ldy=None, name="embed_ln"):
+        """out[r, :width] = LayerNorm((word[ids[r]] + type_row) + pos[pos_ids[r]]) * g + b (AED_OP_EMBED_LN); ids and pos_ids
+        are device int32[rows] the caller has range-checked against word [vocab, width] and pos [npos, width]."""
+        ldy = out.stride(-2) if ldy is None else ldy
+        self._add(L.OP_EMBED_LN, [rows & 0xFFFFFFFF, rows >> 32, width, word.shape[-2], pos.shape[-2], ldy], [eps],
+                  [ids, pos_ids, word, pos, type_row, g, b, out], name=name, nbytes=12 * rows * width)
+        return out
+
+    def gelu_erf(self, x, out, *, rows, width, ld_in=None, ld_out=None, name="gelu_erf"):
+        """out[r, c] = 0.5 x (1 + erf(x / sqrt 2)) of x[r, c] for c < width (AED_OP_GELU_ERF); out may be x."""
+        ld_in = x.stride(-2) if ld_in is None else ld_in
+        ld_out = out.stride(-2) if ld_out is None else ld_out
+        self._add(L.OP_GELU_ERF, [rows & 0xFFFFFFFF, rows >> 32, width, ld_in, ld_out], [], [x, out], name=name,
+                  nbytes=8 * rows * width)
+        return out
+
+    def encoder_attention(self, q, k, v, keymask, out, *, B, H, N, D, ldq, ldk, ldv, ldo, name="encoder_attn"):
+        """softmax(q k^T / sqrt(D) over the keys the mask leaves) v, every row against all N keys of its sequence
+        (AED_OP_ENCODER_ATTENTION): q, k, v are column views of a fused projection buffer [B*N, ld], keymask a device
+        int32[B, N] (0 = the key is left out) or None."""
+        self._add(L.OP_ENCODER_ATTENTION, [B, H, N, D, ldq, ldk, ldv, ldo], [], [q, k, v, keymask, out], name=name,
+                  flops=4 * B * H * N * N * D, nbytes=16 * B * H * N * D)
+        return out
+
     def reflect_pad(self, src, dst, *, B, N, pad, ldd, name="reflect_pad"):
         self._add(L.OP_REFLECT_PAD, [B, N, pad, ldd], [], [src, dst], name=name, nbytes=8 * B * N)
 

@@ -130,16 +130,20 @@ class TextEncoders:
 
     # ------------------------------------------------------------------ loading
     @classmethod
-    def from_pretrained(cls, root: str, kind: str, device="cpu", t5="torch", lm="torch"):
+    def from_pretrained(cls, root: str, kind: str, device="cpu", t5="torch", lm="torch", clap="torch"):
         """Load from a diffusers-style snapshot directory (tokenizer/, text_encoder/, tokenizer_2/, text_encoder_2/,
         language_model/, projection_model/).  Raises if a required sub-directory is missing.  t5="native" puts a
         `t5.NativeT5Encoder` (the encoder stack on the op tape) where the T5 module goes, lm="native" a `lm.NativeGPT2` (the
-        whole continuous generation as one tape) where AudioLDM2's GPT-2 goes; everything else stays."""
+        whole continuous generation as one tape) where AudioLDM2's GPT-2 goes, clap="native" a `clap.NativeClapText` (AudioLDM)
+        or `clap.NativeClapModel` (AudioLDM2) -- the CLAP text tower on the op tape -- where the CLAP module goes; everything
+        else stays."""
         from transformers import AutoTokenizer
         if t5 not in ("torch", "native"):
             raise ValueError(f"t5={t5!r}: expected 'torch' or 'native'")
         if lm not in ("torch", "native"):
             raise ValueError(f"lm={lm!r}: expected 'torch' or 'native'")
+        if clap not in ("torch", "native"):
+            raise ValueError(f"clap={clap!r}: expected 'torch' or 'native'")
 
         def load_t5(path):
             if t5 == "native":
@@ -154,9 +158,13 @@ class TextEncoders:
                 raise FileNotFoundError(f"{root}: text-conditioning component '{sub}' is missing")
             return p
         if kind == "audioldm":
-            from transformers import ClapTextModelWithProjection
-            return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")),
-                       ClapTextModelWithProjection.from_pretrained(need("text_encoder")).to(device), source=root)
+            if clap == "native":
+                from .clap import NativeClapText
+                text_encoder = NativeClapText.from_pretrained(need("text_encoder"), device)
+            else:
+                from transformers import ClapTextModelWithProjection
+                text_encoder = ClapTextModelWithProjection.from_pretrained(need("text_encoder")).to(device)
+            return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")), text_encoder, source=root)
         if kind == "tango":
             return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")), load_t5(need("text_encoder")), source=root)
         if kind == "stable_audio":
@@ -191,8 +199,12 @@ class TextEncoders:
             lm = NativeGPT2.from_pretrained(need("language_model"), device)
         else:
             lm = GPT2Model.from_pretrained(need("language_model")).to(device)
-        return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")),
-                   ClapModel.from_pretrained(need("text_encoder")).to(device),
+        if clap == "native":
+            from .clap import NativeClapModel
+            text_encoder = NativeClapModel.from_pretrained(need("text_encoder"), device)
+        else:
+            text_encoder = ClapModel.from_pretrained(need("text_encoder")).to(device)
+        return cls(kind, AutoTokenizer.from_pretrained(need("tokenizer")), text_encoder,
                    AutoTokenizer.from_pretrained(need("tokenizer_2")),
                    load_t5(need("text_encoder_2")), lm, proj.to(device),
                    max_new_tokens=getattr(lm.config, "max_new_tokens", None) or 8, source=root)

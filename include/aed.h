@@ -219,6 +219,35 @@ enum aed_opcode {
                                  q0 < 0, q0 + Nq > 1024, B or H < 1, a row stride below H*D or no multiple of 4, batch strides
                                  that are negative or no multiple of 4, an out batch stride below one batch item, bsm < Nk,
                                  unaligned q / k / v, more than 2^31 workgroups                                               */
+    /* 45 is unassigned: a record with code 45 is refused as a bad opcode, as it was before 46-48 existed.                   */
+    /* 46-48: what the CLAP text tower (a RoBERTa-style encoder with a pooler and a projection) needs beside the GEMMs and
+       AED_OP_LAYERNORM_ROWS (csrc/clap.hip; audioeditingcode_amd/clap.py builds the tape).  fp32, no atomics, every sum in a
+       fixed order: a launch is bit-repeatable.  Row counts are 64-bit (lo/hi), buffers and row strides are multiples of 4
+       floats and 16-byte aligned (whole rows move as 16-byte accesses).                                                    */
+    AED_OP_EMBED_LN = 46,     /* y[r] = LayerNorm((word[ids[r]] + type_row) + pos[pos_ids[r]]) * g + b, one wave per row: the
+                                 embedding front of a BERT-style encoder with one token type.  The normalisation is that of
+                                 AED_OP_LAYERNORM_ROWS (variance as the mean of the squared deviations from the mean): a sum
+                                 that is constant along the row gives exactly b.  The host range-checks both index vectors
+                                 before upload (an index outside its table adds a zero row and reads nothing).
+                                 slots: p0=ids int32[rows] p1=pos_ids int32[rows] p2=word [vocab][width] p3=pos [npos][width]
+                                 p4=type_row [width] p5=g [width] p6=b [width] p7=y [rows][ldy]; i0,i1=rows lo/hi i2=width
+                                 i3=vocab i4=npos i5=ldy; f0=eps.  Refused: null pointers, rows < 1, a width that is no
+                                 multiple of 32 in [32, 4096], vocab or npos < 1, ldy below the width or no multiple of 4,
+                                 eps <= 0, unaligned pointers                                                                 */
+    AED_OP_GELU_ERF = 47,     /* out = gelu(in) elementwise over the rows of a strided buffer, the exact form gelu(x) = 0.5 x
+                                 (1 + erf(x / sqrt 2)); may run in place.  (The GEMM epilogues have no such activation.)
+                                 slots: p0=in [rows][ld_in] p1=out [rows][ld_out]; i0,i1=rows lo/hi i2=width i3=ld_in i4=ld_out.
+                                 Refused: null pointers, rows < 1, a width or stride that is no multiple of 4, strides below
+                                 the width, unaligned pointers                                                                */
+    AED_OP_ENCODER_ATTENTION = 48, /* out = softmax(q.k^T / sqrt(D) over the keys the mask leaves) . v per (batch item b, head
+                                 h): every query row sees all L keys, there is no bias.  q, k, v are read in place from a fused
+                                 projection buffer: row b*L + i, head h in columns [h*D, (h+1)*D) of each pointer.  A masked
+                                 key (keymask 0) has weight exactly 0, a query row without an attended key gives zeros.  Keys
+                                 run in tiles of 64 with a running maximum and sum.
+                                 slots: p0=q p1=k p2=v p3=keymask int32[B][L] (null: no key masked) p4=out [B*L][ldo]; i0=B
+                                 i1=H i2=L i3=D i4=ldq i5=ldk i6=ldv i7=ldo.  Refused: null pointers (p3 excepted), D outside
+                                 {8, 16, 32, 64}, L outside [1, 512], B or H < 1, a stride below H*D or no multiple of 4,
+                                 unaligned q / k / v, more than 2^31 workgroups                                               */
     AED_OP_COUNT
 };
 
