@@ -46,6 +46,11 @@ LM_ATTN_MAX_NK = 1024                   # its longest key/value cache
 OP_EMBED_LN, OP_GELU_ERF, OP_ENCODER_ATTENTION = 46, 47, 48
 ENC_ATTN_HEAD_SIZES = (8, 16, 32, 64)   # head sizes AED_OP_ENCODER_ATTENTION takes
 ENC_ATTN_MAX_L = 512                    # its longest sequence
+# the CLAP audio tower's ops beside the GEMMs, OP_LAYERNORM_ROWS and OP_GELU_ERF (csrc/swin.hip); tape.window_attention /
+# patch_merge / mel_to_image / mean_tokens name their records.  49 is unassigned (refused as a bad opcode)
+OP_WINDOW_ATTENTION, OP_PATCH_MERGE, OP_MEL_TO_IMAGE, OP_MEAN_TOKENS = 50, 51, 52, 53
+WIN_ATTN_SIDES = (4, 8)                 # window sides AED_OP_WINDOW_ATTENTION takes
+WIN_ATTN_HEAD_SIZES = (8, 16, 24, 32)   # its head sizes
 SEG_MAX_P = 8               # prompts per row AED_OP_REVERSE_STEP_SEGMENTS takes
 PC_TAB_STRIDE = 4           # floats per slot of the ops' table: sqrt(abar_t), c0, c1, sigma_t^2 / const
 PC_MAX_EV = 8               # directions AED_OP_PC_ORTHONORMALISE takes

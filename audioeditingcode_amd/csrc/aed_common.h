@@ -71,6 +71,10 @@ int launch_causal_attention(const aed_op* op, hipStream_t s);
 int launch_embed_ln(const aed_op* op, hipStream_t s);
 int launch_gelu_erf(const aed_op* op, hipStream_t s);
 int launch_encoder_attention(const aed_op* op, hipStream_t s);
+int launch_window_attention(const aed_op* op, hipStream_t s);
+int launch_patch_merge(const aed_op* op, hipStream_t s);
+int launch_mel_to_image(const aed_op* op, hipStream_t s);
+int launch_mean_tokens(const aed_op* op, hipStream_t s);
 
 int aed_num_cus();
 

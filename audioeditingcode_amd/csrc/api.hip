@@ -66,6 +66,8 @@ static launcher_t g_table[AED_OP_COUNT] = {
     launch_layernorm_rows, launch_add_rows, launch_gelu_new, launch_causal_attention,
     nullptr,              // 45 is unassigned (refused as a bad opcode)
     launch_embed_ln, launch_gelu_erf, launch_encoder_attention,
+    nullptr,              // 49 is unassigned (refused as a bad opcode)
+    launch_window_attention, launch_patch_merge, launch_mel_to_image, launch_mean_tokens,
 };
 
 extern "C" {

@@ -22,6 +22,7 @@ hipcc $FLAGS -c resample.hip -o obj/resample.o & pids+=($!)
 hipcc $FLAGS -c t5.hip -o obj/t5.o & pids+=($!)
 hipcc $FLAGS -c lm.hip -o obj/lm.o & pids+=($!)
 hipcc $FLAGS -c clap.hip -o obj/clap.o & pids+=($!)
+hipcc $FLAGS -c swin.hip -o obj/swin.o & pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 hipcc --offload-arch=$ARCH -shared -fPIC obj/*.o -o ../libaed.so
 echo "built $(cd .. && pwd)/libaed.so"

@@ -712,6 +712,35 @@ class Tape:
                   flops=4 * B * H * N * N * D, nbytes=16 * B * H * N * D)
         return out
 
+    # ------------------------------------------------------------------ CLAP audio tower ops (csrc/swin.hip)
+    def window_attention(self, q, k, v, bias, out, *, B, H, W, M, s, nH, D, ldq, ldk, ldv, ldo, name="window_attn"):
+        """Swin attention over the M x M windows of a [B, H, W] token map shifted by s (AED_OP_WINDOW_ATTENTION): q, k, v are
+        column views of the fused projection buffer [B*H*W, ld], bias the expanded relative-position bias [nH, M*M, M*M]."""
+        self._add(L.OP_WINDOW_ATTENTION, [B, H, W, M, s, nH, D, ldq, ldk, ldv, ldo], [], [q, k, v, bias, out], name=name,
+                  flops=4 * B * H * W * M * M * nH * D, nbytes=16 * B * H * W * nH * D)
+        return out
+
+    def patch_merge(self, x, g, b, out, *, B, H, W, C, eps, ldx=None, ldy=None, name="patch_merge"):
+        """out[(b, h', w')] = LayerNorm(concat of x rows (2h'+r, 2w'+c), (r, c) = (0,0), (1,0), (0,1), (1,1)) * g + b
+        (AED_OP_PATCH_MERGE); x is [B*H*W, ldx], out [B*(H/2)*(W/2), ldy] with 4C values a row."""
+        ldx = x.stride(-2) if ldx is None else ldx
+        ldy = out.stride(-2) if ldy is None else ldy
+        self._add(L.OP_PATCH_MERGE, [B, H, W, C, ldx, ldy], [eps], [x, g, b, out], name=name, nbytes=8 * B * H * W * C)
+        return out
+
+    def mel_to_image(self, x, a, c, out, *, B, T, F, S, ratio, name="mel_to_image"):
+        """out [B, S, S] = fold(stretch(x * a[f] + c[f])) of x [B, T, F] (AED_OP_MEL_TO_IMAGE): the batch norm in eval mode, the
+        bicubic stretch to S * (S / F) frames and the mel-to-image fold of the audio encoder's front."""
+        self._add(L.OP_MEL_TO_IMAGE, [B, T, F, S, ratio], [], [x, a, c, out], name=name, nbytes=4 * B * (T * F + S * S))
+        return out
+
+    def mean_tokens(self, x, out, *, B, L_, C, ldx=None, ldo=None, name="mean_tokens"):
+        """out[b, c] = mean over the L_ rows b*L_ .. b*L_ + L_ - 1 of x[:, c] (AED_OP_MEAN_TOKENS)."""
+        ldx = x.stride(-2) if ldx is None else ldx
+        ldo = out.stride(-2) if ldo is None else ldo
+        self._add(L.OP_MEAN_TOKENS, [B, L_, C, ldx, ldo], [], [x, out], name=name, nbytes=4 * B * (L_ + 1) * C)
+        return out
+
     def reflect_pad(self, src, dst, *, B, N, pad, ldd, name="reflect_pad"):
         self._add(L.OP_REFLECT_PAD, [B, N, pad, ldd], [], [src, dst], name=name, nbytes=8 * B * N)
 

@@ -248,6 +248,44 @@ enum aed_opcode {
                                  i1=H i2=L i3=D i4=ldq i5=ldk i6=ldv i7=ldo.  Refused: null pointers (p3 excepted), D outside
                                  {8, 16, 32, 64}, L outside [1, 512], B or H < 1, a stride below H*D or no multiple of 4,
                                  unaligned q / k / v, more than 2^31 workgroups                                               */
+    /* 49 is unassigned: a record with code 49 is refused as a bad opcode, as it was before 50-53 existed.                   */
+    /* 50-53: what the CLAP audio tower (HTSAT, a Swin transformer over a log-mel spectrogram folded into an image) needs
+       beside the GEMMs, AED_OP_LAYERNORM_ROWS and AED_OP_GELU_ERF (csrc/swin.hip; audioeditingcode_amd/clap_audio.py builds
+       the tape).  fp32, no atomics, every sum in a fixed order: a launch is bit-repeatable.  Buffers and row strides are
+       multiples of 4 floats and 16-byte aligned.                                                                           */
+    AED_OP_WINDOW_ATTENTION = 50, /* Swin attention over M x M windows of a [B][H][W] token map, read in place from the fused
+                                 q|k|v buffer: token (b, h, w) is row (b*H + h)*W + w, head n in columns [n*D, (n+1)*D) of each
+                                 pointer.  The roll by -s, the window partition, the window reverse and the roll back are
+                                 address arithmetic: hs = (h - s) mod H, ws = (w - s) mod W, window (hs / M, ws / M), index
+                                 inside the window (hs mod M)*M + (ws mod M), region 3*[(hs >= H-M) + (hs >= H-s)] + [(ws >= W-M)
+                                 + (ws >= W-s)].  score = q.k / sqrt(D) + bias[n][query][key], plus -100.0 (added, not a hard
+                                 mask) when s > 0 and the two regions differ; softmax over the M*M keys of the window; the
+                                 context row is written at the token's own row of out.  One wave per (window, head).
+                                 slots: p0=q p1=k p2=v p3=bias [nH][M*M][M*M] p4=out [B*H*W][ldo]; i0=B i1=H i2=W i3=M i4=s
+                                 i5=nH i6=D i7=ldq i8=ldk i9=ldv i10=ldo.  Refused: null pointers, M outside {4, 8}, D outside
+                                 {8, 16, 24, 32}, s outside [0, M), B or nH < 1, H or W no positive multiple of M, a stride
+                                 below nH*D or no multiple of 4, unaligned pointers, more than 2^31 workgroups                */
+    AED_OP_PATCH_MERGE = 51,  /* Swin's patch merging without its Linear: output row (b, h', w') is the concatenation of the
+                                 input rows (2h'+r, 2w'+c) in the order (r, c) = (0,0), (1,0), (0,1), (1,1), then LayerNorm over
+                                 the 4C values (the normalisation of AED_OP_LAYERNORM_ROWS: variance as the mean of the squared
+                                 deviations from the mean).  One wave per output row.
+                                 slots: p0=x [B*H*W][ldx] p1=g [4C] p2=b [4C] p3=y [B*(H/2)*(W/2)][ldy]; i0=B i1=H i2=W i3=C
+                                 i4=ldx i5=ldy; f0=eps.  Refused: null pointers, B < 1, odd H or W, a C that is no multiple of
+                                 8 in [8, 1024], ldx below C, ldy below 4C, strides that are no multiple of 4, eps <= 0,
+                                 unaligned pointers                                                                           */
+    AED_OP_MEL_TO_IMAGE = 52, /* the front of the audio encoder in one launch: eval-mode batch norm per mel bin (x*a[f] + c[f],
+                                 a and c folded on the host), a bicubic stretch along time to Wd = S*(S/F) frames when T < Wd
+                                 (align_corners: src = i*(T-1)/(Wd-1), taps floor(src)-1 .. floor(src)+2 clamped to [0, T-1],
+                                 Keys' cubic with A = -0.75), and the fold img[h][w] = xs[(h / F)*S + w][h mod F].  The output
+                                 [B][S][S] is NHWC with one channel.
+                                 slots: p0=x [B][T][F] p1=a [F] p2=c [F] p3=out [B][S][S]; i0=B i1=T i2=F i3=S i4=freq_ratio.
+                                 Refused: null pointers, B, F or S < 1, S no multiple of F, F != S / freq_ratio, T outside
+                                 [1, Wd], unaligned pointers                                                                  */
+    AED_OP_MEAN_TOKENS = 53,  /* out[b][c] = mean over l < L of x[b*L + l][c], summed in a fixed order (16 strided partial sums
+                                 per column, added in order).
+                                 slots: p0=x [B*L][ldx] p1=out [B][ldo]; i0=B i1=L i2=C i3=ldx i4=ldo.  Refused: null pointers,
+                                 B outside [1, 65535], L < 1, a C that is no positive multiple of 4, strides below C or no
+                                 multiple of 4, unaligned pointers                                                            */
     AED_OP_COUNT
 };
 
